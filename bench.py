@@ -26,7 +26,17 @@ Multi-GPU: one process per GPU.  Under torchrun the ranks come from its env;
 across ranks with no data-path collective ("scaling": "weak"); RCCL only for
 the barrier, the max-over-ranks timing reduction and the device-name gather.
 
-Rank 0 prints ONE JSON line.  `roofline` is the dominant kernel (RANSAC
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the
+``--steps`` steps and prints the headline fields (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, the workload, the process group
+and the gathered inlier counts).  ``--dump-outputs DIR`` also writes what the
+last timed step returned (E, P, inlier counts, a fixed seeded sample of the
+cost volume) as DIR/<name>.npy; the inputs are seeded, so two builds run with
+the same arguments can be compared output for output.  Everything else (the
+fields below) takes runs of its own after the timed region and is measured
+only with ``--full``.
+
+With ``--full``: `roofline` is the dominant kernel (RANSAC
 scoring: k_score_mf on the f16 matrix cores, or k_score32 on the fp32 VALU
 when the matrix-core scorer is off); `roofline_sweep` the HBM-bound
 cost-volume kernel; both
@@ -35,7 +45,8 @@ every launch on the launching stream during the timed region; `traffic` is
 the PMC-measured HBM bytes per launch (FETCH_SIZE x2 + WRITE_SIZE, gfx950
 correction) from the committed profiles/rNN_pmc*.json of the same workload.
 The `cpu_baseline` is the oracle (CPU restatement) on one full pair, rank 0 at
-N=1 only.
+N=1 only (``--no-cpu-baseline`` / ``--no-regularize`` drop that leg / the PSNet
+regularisation lines from a ``--full`` run).
 """
 import argparse
 import json
@@ -77,9 +88,17 @@ def parse(argv=None):
     ap.add_argument("--iters", type=int, default=None, help="ransac_iter (H = 512 x iters)")
     ap.add_argument("--threshold", type=float, default=1e-4)
     ap.add_argument("--cost-dtype", choices=["fp32", "bf16"], default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure what takes runs of its own: the per-kernel and "
+                         "roofline figures (a fully evented pass), the PSNet regularisation rooflines in four "
+                         "precisions and the CPU baseline; a plain run reports the headline fields only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (E, P, inliers in float64; "
+                         "cost_sample: a fixed seeded sample of the cost volume in float32); the inputs are "
+                         "seeded, so runs with the same arguments are comparable output for output")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-regularize", action="store_true",
-                    help="skip the (unscored) PSNet 3-D regularisation roofline line after the timed region")
+                    help="with --full: skip the (unscored) PSNet 3-D regularisation roofline lines")
     ap.add_argument("--fused", action="store_true",
                     help="(the default for dense flow since round 6) RANSAC reads the flow directly "
                          "(sfm_ransac5_flow, SURVEY 8f row 2) instead of materialised correspondences")
@@ -436,6 +455,34 @@ def regularize_roofline(cost, steps=3, precision="bf16"):
             "note": "not part of value: the CNN after the measured path, timed after it"}
 
 
+DUMP_SAMPLE = 1 << 22        # elements kept of an output larger than that (16 MiB in float32)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(dirname, rank, outputs):
+    """--dump-outputs: every array of ``outputs`` (name -> tensor, what the
+    timed path's last step returned) as <dirname>/<name>.npy (rank 0; the
+    other ranks add _rank<r>).  Floating-point tensors narrower than float64
+    are written as float32, float64 and integer ones as float64.  An output of
+    more than DUMP_SAMPLE elements is written as <name>_sample: its flattened
+    elements at DUMP_SAMPLE indices drawn (with replacement) by a CPU
+    generator seeded with DUMP_SEED, the same indices for the same shape in
+    every run and build."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in outputs.items():
+        t = t.detach()
+        wide = t.dtype == torch.float64 or not t.dtype.is_floating_point
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=g)
+            t = t.reshape(-1)[idx.to(t.device)]
+            name += "_sample"
+        a = t.to(torch.float64 if wide else torch.float32).cpu().numpy()
+        np.save(os.path.join(dirname, name + ("" if rank == 0 else f"_rank{rank}") + ".npy"), a)
+
+
 def rank_device_index(local):
     """The GPU a rank drives: its LOCAL_RANK (one process per GPU of the node;
     dist.init binds the RCCL communicator to the same index).  Under
@@ -492,6 +539,8 @@ def _main_stub(args, dist):
     dist.barrier()
     elapsed = dist.reduce_max(time.perf_counter() - t0)
     names = dist.device_names(None)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, {"x": x})
     # the same per-pair gather as the GPU path: rows tagged (rank, device index, pair)
     di = rank_device_index(_local)
     rows = torch.tensor([[float(rank), float(di), float(i)] for i in range(args.batch)], dtype=torch.float64)
@@ -510,9 +559,81 @@ def _main_stub(args, dist):
     return 0
 
 
+def kernel_report(args, hp, stepf, inputs, dev, B, C, fhw, cost_dtype):
+    """--full: the per-kernel and roofline fields of the line.  The two roofline
+    kernels' launch times are the HIP events of the timed region (read here);
+    the other stages' come from a fully evented pass of its own, run here."""
+    import torch
+    from sfm_amd import _lib, ransac
+    kt = {}
+    for name in ROOFLINE_REGIONS:
+        ms, n = _lib.profile_read(name)
+        if n:
+            kt[name] = ms / n
+    # the other stages' launch times: a separate, fully evented pass after the
+    # timed region (same inputs and outputs; never part of `value`)
+    kt_all = profiled_pass(stepf, inputs, min(args.steps, 5), dev)
+    cands = ransac.candidate_counts(hp.ws, B, args.iters)
+    evals = sum(cands) * hp.n                       # candidate E x correspondences per launch
+    skipped = ransac.skipped_evaluations(hp.ws, B, args.iters)   # exact bound pruning (last launch)
+    done = evals - skipped                          # evaluations the launch performed
+    upper_work = None
+    if _lib.last_scorer() == "k_score_mf2+prune" and _lib.tune_get("score_mf_prune_upper"):
+        # every evaluation not skipped took the one-sided test (all candidates
+        # before the pruning point, the first keep's survivors after it); the
+        # finally kept candidates were then counted exactly over every point
+        kept = ransac.kept_candidates(hp.ws, B, args.iters)
+        upper_work = (done, int(kept.sum()) * hp.n, int(kept.sum()))
+    score_ms = kt["ransac_score"]
+    score_tflops = done * FLOP_PER_EVAL / (score_ms * 1e-3) / 1e12
+    use_mf = bool(_lib.tune_get("score_mf")) and 2.0 ** -15 <= args.threshold < 1.0
+    h, w = fhw
+    s = 4 if cost_dtype == torch.float32 else 2
+    if args.overlap_ref != "0":
+        # the sweep kernel writes the warped half (and reads tgt); the reference
+        # half (writes + its padded ref reads) is k_ref_planes' on the side stream
+        sweep_bytes = B * (C * args.nlabel * h * w * s + C * h * w * 4)
+        ref_bytes = B * (C * args.nlabel * h * w * s + C * h * w * 4)
+    else:
+        sweep_bytes = B * (2 * C * args.nlabel * h * w * s + 2 * C * h * w * 4)
+    sweep_gbs = sweep_bytes / (kt["plane_sweep"] * 1e-3) / 1e9
+    hyps = B * 512 * args.iters
+
+    traffic, traffic_src = pmc_traffic(args)
+    return {
+        "roofline": score_roofline(use_mf, score_tflops, done, evals, skipped, sum(cands), hp.n, score_ms,
+                                   traffic.get("ransac_score"), traffic_src,
+                                   rocprof_kernel_ms(args, ("k_mf_cands", "k_score_mf2"),
+                                                     optional=("k_mf2_split", "k_mf2_lead", "k_mf2_keep",
+                                                               "k_mf2_keep_map", "k_mf2_zero_kept",
+                                                               "k_mf2_exact")),
+                                   _lib.last_scorer(), upper_work),
+        "roofline_sweep": {"kernel": "plane_sweep", "bound": "hbm", "achieved": round(sweep_gbs, 1),
+                           "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(sweep_gbs / PEAK_HBM_GBS, 4),
+                           "traffic": traffic.get("plane_sweep"), "traffic_source": traffic_src,
+                           "avg_launch_ms": round(kt["plane_sweep"], 4),
+                           "bytes_per_launch": sweep_bytes},
+        "roofline_ref_planes": ({"kernel": "ref_planes (k_ref_pad + k_ref_planes, side stream beside the scorer)",
+                                 "bound": "hbm", "avg_launch_ms": round(kt["ref_planes"], 4),
+                                 "bytes_per_launch": ref_bytes,
+                                 "achieved": round(ref_bytes / (kt["ref_planes"] * 1e-3) / 1e9, 1),
+                                 "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                                 "note": "runs concurrently with k_score_mf2: its duration includes sharing "
+                                         "the CUs with the scorer; not on the step's critical path"}
+                                if args.overlap_ref != "0" and "ref_planes" in kt else None),
+        "solve": {"hypotheses_per_launch": hyps, "ms": round(kt_all["ransac_solve"], 4),
+                  "hypotheses_per_s": round(hyps / (kt_all["ransac_solve"] * 1e-3), 1)},
+        "kernel_ms": {k: round(v, 4) for k, v in {**kt_all, **kt}.items()},
+        "kernel_ms_source": (f"{', '.join(ROOFLINE_REGIONS)}: HIP events in the timed region; the other stages: "
+                             f"HIP events around every stage in a separate pass of {min(args.steps, 5)} steps "
+                             f"after it (fully evented steps run the scorer slower, "
+                             f"{kt_all.get('ransac_score', 0.0):.3f} ms there)"),
+    }
+
+
 def _main_gpu(args, dist):
     import torch
-    from sfm_amd import _lib, ransac, synth
+    from sfm_amd import _lib, synth
     from sfm_amd.pipeline import TwoViewHotPath
     rank, world, local = dist.init(backend="gloo" if _shared_gpu() else None)
     dev = torch.device("cuda", rank_device_index(local))
@@ -549,7 +670,9 @@ def _main_gpu(args, dist):
     torch.cuda.synchronize(dev)
     # HIP events inside the timed region only around the two roofline kernels:
     # every evented launch adds two event records to the stream (sparse step
-    # 1.722 -> 1.772 ms with all seven regions evented, git-history scripts/event_ab.py)
+    # 1.722 -> 1.772 ms with all seven regions evented, git-history scripts/event_ab.py).
+    # A plain run keeps them too (only --full reads them), so that `value` is
+    # measured on the same timed region with and without --full
     _lib.profile_reset()
     _lib.profile_select(ROOFLINE_REGIONS)
     _lib.profile_enable(True)
@@ -569,41 +692,14 @@ def _main_gpu(args, dist):
     rows = torch.cat([E.reshape(B, 9), P.reshape(B, 12), inl.reshape(B, 1).double()], 1)
     gathered = dist.gather_rows(rows, world).cpu()
 
-    kt = {}
-    for name in ROOFLINE_REGIONS:
-        ms, n = _lib.profile_read(name)
-        if n:
-            kt[name] = ms / n
-    # the other stages' launch times: a separate, fully evented pass after the
-    # timed region (same inputs and outputs; never part of `value`)
-    kt_all = profiled_pass(stepf, (flow, K, ref_fea, tgt_fea), min(args.steps, 5), dev)
-    cands = ransac.candidate_counts(hp.ws, B, args.iters)
-    evals = sum(cands) * hp.n                       # candidate E x correspondences per launch
-    skipped = ransac.skipped_evaluations(hp.ws, B, args.iters)   # exact bound pruning (last launch)
-    done = evals - skipped                          # evaluations the launch performed
-    upper_work = None
-    if _lib.last_scorer() == "k_score_mf2+prune" and _lib.tune_get("score_mf_prune_upper"):
-        # every evaluation not skipped took the one-sided test (all candidates
-        # before the pruning point, the first keep's survivors after it); the
-        # finally kept candidates were then counted exactly over every point
-        kept = ransac.kept_candidates(hp.ws, B, args.iters)
-        upper_work = (done, int(kept.sum()) * hp.n, int(kept.sum()))
-    score_ms = kt["ransac_score"]
-    score_tflops = done * FLOP_PER_EVAL / (score_ms * 1e-3) / 1e12
-    use_mf = bool(_lib.tune_get("score_mf")) and 2.0 ** -15 <= args.threshold < 1.0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, {"E": E, "P": P, "inliers": inl, "cost": cost})
+    # --full: what takes runs of its own after the timed region (every rank, as the timed steps)
+    report = (kernel_report(args, hp, stepf, (flow, K, ref_fea, tgt_fea), dev, B, C, fhw, cost_dtype)
+              if args.full else {})
     h, w = fhw
     s = 4 if cost_dtype == torch.float32 else 2
-    if args.overlap_ref != "0":
-        # the sweep kernel writes the warped half (and reads tgt); the reference
-        # half (writes + its padded ref reads) is k_ref_planes' on the side stream
-        sweep_bytes = B * (C * args.nlabel * h * w * s + C * h * w * 4)
-        ref_bytes = B * (C * args.nlabel * h * w * s + C * h * w * 4)
-    else:
-        sweep_bytes = B * (2 * C * args.nlabel * h * w * s + 2 * C * h * w * 4)
-    sweep_gbs = sweep_bytes / (kt["plane_sweep"] * 1e-3) / 1e9
-    hyps = B * 512 * args.iters
 
-    traffic, traffic_src = pmc_traffic(args)
     if rank == 0:
         pairs = world * B * args.steps
         corr = (f"{args.keypoints} SIFT-like keypoints" if args.keypoints
@@ -636,46 +732,21 @@ def _main_gpu(args, dist):
             "dist": {"world_size": torch.distributed.get_world_size() if torch.distributed.is_initialized() else 1,
                      "backend": torch.distributed.get_backend() if torch.distributed.is_initialized() else None,
                      "devices": names},
-            "roofline": score_roofline(use_mf, score_tflops, done, evals, skipped, sum(cands), hp.n, score_ms,
-                                       traffic.get("ransac_score"), traffic_src,
-                                       rocprof_kernel_ms(args, ("k_mf_cands", "k_score_mf2"),
-                                                         optional=("k_mf2_split", "k_mf2_lead", "k_mf2_keep",
-                                                                   "k_mf2_keep_map", "k_mf2_zero_kept",
-                                                                   "k_mf2_exact")),
-                                       _lib.last_scorer(), upper_work),
-            "roofline_sweep": {"kernel": "plane_sweep", "bound": "hbm", "achieved": round(sweep_gbs, 1),
-                               "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(sweep_gbs / PEAK_HBM_GBS, 4),
-                               "traffic": traffic.get("plane_sweep"), "traffic_source": traffic_src,
-                               "avg_launch_ms": round(kt["plane_sweep"], 4),
-                               "bytes_per_launch": sweep_bytes},
-            "roofline_ref_planes": ({"kernel": "ref_planes (k_ref_pad + k_ref_planes, side stream beside the scorer)",
-                                     "bound": "hbm", "avg_launch_ms": round(kt["ref_planes"], 4),
-                                     "bytes_per_launch": ref_bytes,
-                                     "achieved": round(ref_bytes / (kt["ref_planes"] * 1e-3) / 1e9, 1),
-                                     "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                                     "note": "runs concurrently with k_score_mf2: its duration includes sharing "
-                                             "the CUs with the scorer; not on the step's critical path"}
-                                    if args.overlap_ref != "0" and "ref_planes" in kt else None),
-            "solve": {"hypotheses_per_launch": hyps, "ms": round(kt_all["ransac_solve"], 4),
-                      "hypotheses_per_s": round(hyps / (kt_all["ransac_solve"] * 1e-3), 1)},
-            "kernel_ms": {k: round(v, 4) for k, v in {**kt_all, **kt}.items()},
-            "kernel_ms_source": (f"{', '.join(ROOFLINE_REGIONS)}: HIP events in the timed region; the other stages: "
-                                 f"HIP events around every stage in a separate pass of {min(args.steps, 5)} steps "
-                                 f"after it (fully evented steps run the scorer slower, "
-                                 f"{kt_all.get('ransac_score', 0.0):.3f} ms there)"),
+            **report,
             "inliers": [int(v) for v in gathered[:, 21].tolist()],
             "gathered": {"pairs": int(gathered.shape[0]), "per_rank": [len(dist.shard(world * B, r, world))
                                                                        for r in range(world)],
                          "via": "dist.gather_rows (all_gather of E[9], P[12], inliers per pair)"},
         }
-        if world == 1 and not args.no_regularize and hp.cost.dtype in (torch.float32, torch.bfloat16):
+        regularize = args.full and world == 1 and not args.no_regularize
+        if regularize and hp.cost.dtype in (torch.float32, torch.bfloat16):
             for prec, key in (("bf16", "roofline_regularize"), ("fp16", "roofline_regularize_fp16"),
                               ("fp32", "roofline_regularize_fp32"), ("fp32x3", "roofline_regularize_fp32x3")):
                 try:
                     out[key] = regularize_roofline(hp.cost, steps=2 if prec == "fp32" else 3, precision=prec)
                 except Exception as e:   # extra information, never the metric
                     out[key] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:   # rank 0 at N=1 only
+        if args.full and world == 1 and not args.no_cpu_baseline:   # rank 0 at N=1 only
             try:
                 out["cpu_baseline"] = cpu_baseline(flow, K, ref_fea, tgt_fea, P.float(), args,
                                                    n_pts=args.keypoints or None, keypoints=kp)

@@ -10,7 +10,7 @@ mkdir -p gpurun_out
 i=0
 for t in "$@"; do
   tune=$t; [ "$t" = "-" ] && tune=""
-  timeout -k 10 200 python -u bench.py --config $CONFIG --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline \
+  timeout -k 10 200 python -u bench.py --full --config $CONFIG --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline \
       --no-regularize ${tune:+--tune $tune} > gpurun_out/${TAG}_ab_$i.log 2>&1 || { tail -20 gpurun_out/${TAG}_ab_$i.log; exit 1; }
   python - gpurun_out/${TAG}_ab_$i.log "$t" <<'PY'
 import json, sys

@@ -8,7 +8,7 @@ TAG=${TAG:-r05}
 mkdir -p gpurun_out
 i=0
 for a in "$@"; do
-  timeout -k 10 200 python -u bench.py --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-regularize $a \
+  timeout -k 10 200 python -u bench.py --full --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-regularize $a \
       > gpurun_out/${TAG}_abx_$i.log 2>&1 || { tail -20 gpurun_out/${TAG}_abx_$i.log; exit 1; }
   python - gpurun_out/${TAG}_abx_$i.log "$a" <<'PY'
 import json, sys

@@ -12,7 +12,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   for spec in "$@"; do
     lib=${spec%%@*}; tune=""; [ "$lib" != "$spec" ] && tune=${spec#*@}
     if [ "$lib" = "-" ]; then unset SFM_HIP_LIB; else export SFM_HIP_LIB=$lib; fi
-    timeout -k 10 200 python -u bench.py --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-regularize \
+    timeout -k 10 200 python -u bench.py --full --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline --no-regularize \
         ${BENCH_ARGS:-} ${tune:+--tune $tune} > gpurun_out/${TAG}_abl_$i.log 2>&1 || { tail -20 gpurun_out/${TAG}_abl_$i.log; exit 1; }
     python - gpurun_out/${TAG}_abl_$i.log "$spec" <<'PY'
 import json, sys

@@ -9,6 +9,7 @@
 set -u
 R=${R:-r06}
 mkdir -p gpurun_out
+OUT=$_        # the log folder made above
 export PYTHONDONTWRITEBYTECODE=1
 if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --timeout 300 --timeout-method thread \
@@ -18,14 +19,14 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
       || { tail -20 gpurun_out/${R}_smoke.log; exit 1; }
   tail -1 gpurun_out/${R}_smoke.log
 fi
-timeout -k 10 500 python -u bench.py --steps ${STEPS:-20} --warmup 3 > gpurun_out/${R}_bench_c2.log 2>&1 \
-    || { tail -20 gpurun_out/${R}_bench_c2.log; exit 1; }
+timeout -k 10 500 python -u bench.py --full --steps ${STEPS:-20} --warmup 3 > $OUT/${R}_bench_c2.log 2>&1 \
+    || { tail -20 $OUT/${R}_bench_c2.log; exit 1; }
 grep '^{' gpurun_out/${R}_bench_c2.log | cut -c1-400
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 if [ "${SKIP_PROF:-0}" != "1" ]; then
   for cfg in c2 sparse c3; do
     timeout -k 10 400 rocprofv3 --kernel-trace --stats -d gpurun_out/${R}_prof_$cfg -o run --output-format csv -- \
-        python3 bench.py --config $cfg --steps 10 --warmup 2 --no-cpu-baseline --no-regularize \
+        python3 bench.py --full --config $cfg --steps 10 --warmup 2 --no-cpu-baseline --no-regularize \
         > gpurun_out/${R}_prof_$cfg.log 2>&1 || { tail -20 gpurun_out/${R}_prof_$cfg.log; exit 1; }
     find gpurun_out/${R}_prof_$cfg -name "*kernel_stats*"
   done
@@ -38,7 +39,7 @@ if [ "${SKIP_PMC:-0}" != "1" ]; then
 fi
 if [ "${SKIP_CONFIGS:-0}" != "1" ]; then
   for cfg in sparse c3 c4 c5; do
-    timeout -k 10 300 python -u bench.py --config $cfg --steps 20 --warmup 3 --no-cpu-baseline --no-regularize \
+    timeout -k 10 300 python -u bench.py --full --config $cfg --steps 20 --warmup 3 --no-cpu-baseline --no-regularize \
         > gpurun_out/${R}_bench_$cfg.log 2>&1 || { tail -20 gpurun_out/${R}_bench_$cfg.log; exit 1; }
     grep '^{' gpurun_out/${R}_bench_$cfg.log | cut -c1-300
   done

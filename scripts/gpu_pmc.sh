@@ -6,7 +6,7 @@ OUT=${PMC_OUT:-gpurun_out/pmc}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 rocprofv3 -L > $OUT/counters_list.txt 2>&1 || true
-ARGS="python3 bench.py --config ${CONFIG:-c2} --steps 1 --warmup 1 --no-cpu-baseline --no-regularize"
+ARGS="python3 bench.py --full --config ${CONFIG:-c2} --steps 1 --warmup 1 --no-cpu-baseline --no-regularize"
 i=0
 for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_WAVES GRBM_GUI_ACTIVE" \
            "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU" \

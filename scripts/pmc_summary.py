@@ -96,7 +96,7 @@ def main(src, dst, config="c2"):
         out[k] = d
     b, it, nl, cd = WORKLOADS[config]
     json.dump({"source": "rocprofv3 --pmc --kernel-trace, separate passes (scripts/gpu_pmc.sh) over "
-                         f"`python3 bench.py --config {config} --steps 1 --warmup 1 --no-cpu-baseline`",
+                         f"`python3 bench.py --full --config {config} --steps 1 --warmup 1 --no-cpu-baseline`",
                "workload": {"config": config, "batch": b, "nlabel": nl, "iters": it, "cost_dtype": cd},
                "src_hash": _src_hash(src),
                "kernels": out}, open(dst, "w"), indent=1, sort_keys=True)

@@ -62,6 +62,53 @@ def test_single_rank_default():
     assert out["config"]["name"] == "c2" and out["config"]["pairs_per_gpu"] == 8
 
 
+def test_dump_outputs_writes_every_ranks_arrays(tmp_path):
+    """--dump-outputs DIR: rank 0 writes DIR/<name>.npy, the other ranks
+    DIR/<name>_rank<r>.npy, float32 here; the stub's inputs are seeded per
+    rank, so a second run with the same arguments writes the same arrays."""
+    import numpy as np
+    runs = []
+    for d in ("a", "b"):
+        r = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr
+        assert _json_line(r.stdout)["steps"] == 3
+        assert sorted(os.listdir(tmp_path / d)) == ["x.npy", "x_rank1.npy"]
+        runs.append([np.load(tmp_path / d / n) for n in ("x.npy", "x_rank1.npy")])
+    assert all(a.dtype == np.float32 and a.shape == (64, 64) for a in runs[0])
+    assert all(np.array_equal(a, b) for a, b in zip(*runs))
+    assert not np.array_equal(runs[0][0], runs[0][1])
+
+
+def test_full_is_an_option_off_by_default():
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse([]).full is False and bench.parse([]).dump_outputs is None
+    assert bench.parse(["--full", "--no-cpu-baseline"]).full is True
+    r = _run(["--steps", "1", "--warmup", "0", "--full"])
+    assert r.returncode == 0, r.stderr
+
+
+def test_dump_samples_a_large_output_at_fixed_indices(tmp_path):
+    """An output above DUMP_SAMPLE elements is written as <name>_sample: the
+    same seeded indices on every call; float64 and integers go out as float64,
+    narrower floats as float32."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(bench.DUMP_SAMPLE + 7, dtype=torch.float32).to(torch.bfloat16)
+    outs = {"big": big, "n": torch.arange(5, dtype=torch.int32), "d": torch.ones(2, 3, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "a"), 0, outs)
+    bench.dump_outputs(str(tmp_path / "b"), 0, outs)
+    assert sorted(os.listdir(tmp_path / "a")) == ["big_sample.npy", "d.npy", "n.npy"]
+    a, b = (np.load(tmp_path / d / "big_sample.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_SAMPLE,) and np.array_equal(a, b)
+    idx = torch.randint(big.numel(), (bench.DUMP_SAMPLE,), generator=torch.Generator().manual_seed(bench.DUMP_SEED))
+    assert np.array_equal(a, big[idx].float().numpy())
+    n, d = np.load(tmp_path / "a" / "n.npy"), np.load(tmp_path / "a" / "d.npy")
+    assert n.dtype == np.float64 and n.tolist() == [0, 1, 2, 3, 4] and d.dtype == np.float64 and d.shape == (2, 3)
+
+
 def test_gpus_and_world_size_mismatch_fails():
     r = _run(["--gpus", "2", "--steps", "1"], extra_env={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode == 2

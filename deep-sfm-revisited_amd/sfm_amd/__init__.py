@@ -7,7 +7,8 @@ libsfm_hip.so (include/sfm_hip.h):
   regularize  PSNet 3-D cost regularisation (dres0..classify) on the matrix cores
   synth    seeded synthetic KITTI-shaped inputs
   dist     one-process-per-GPU pair sharding and RCCL metric gather
+  validate the validation loop and its fused depth-metric rows (main.py:477-601)
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["ransac", "sweep", "regularize", "synth", "dist", "config"]
+__all__ = ["ransac", "sweep", "regularize", "synth", "dist", "config", "validate"]

@@ -89,6 +89,11 @@ _SIGS = [
      [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     ("sfm_kinv3x3", ctypes.c_int, [_c_dp, ctypes.c_int, _c_dp, _c_dp]),
     ("sfm_flow2depth", ctypes.c_int, [_c_dp, _c_dp, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp]),
+    ("sfm_depth_metrics_workspace_bytes", ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    ("sfm_depth_metrics", ctypes.c_int,
+     [_c_dp, ctypes.c_int64, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, ctypes.c_int,
+      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, _c_dp, _c_dp, _c_dp,
+      ctypes.c_size_t, _c_dp]),
     ("sfm_conv3_bf16", ctypes.c_int,
      [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_dp,
       ctypes.c_int, ctypes.c_int, _c_dp, _c_dp]),

@@ -42,6 +42,7 @@ def defaults():
         PSNET_DEP_CONTEXT=False,  # lib/config.py:47
         IND_CONTEXT=False,        # lib/config.py:164
         CONTEXT_BN=False,         # lib/config.py:158
+        DEMON_DATASET=False,      # lib/config.py:120 (main.py:565: DeMoN masking in validate)
     )
 
 

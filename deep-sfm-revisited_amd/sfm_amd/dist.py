@@ -1,6 +1,8 @@
 """One process per GPU: image pairs shard across ranks with no data-path
 collective; RCCL (backend "nccl" on ROCm) or gloo is used only to gather
-per-pair outputs / validation metrics to rank 0 and to reduce timings.
+per-pair outputs (E, P, inliers) and the validation metric rows of
+sfm_amd.validate (float64, one row per pair) to every rank, and to reduce
+timings.
 
 Replaces the reference's single-process torch.nn.DataParallel (main.py:219),
 whose implicit per-forward parameter broadcast / scatter / gather has no

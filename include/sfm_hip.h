@@ -353,6 +353,43 @@ int sfm_inverse_warp(const float* feat, int batch, int channels, int h, int w,
 int sfm_flow2depth(const float* KR, const float* KT, const float* Kinv, int batch, int H, int W, float* out,
                    void* stream);
 
+/* ------------------------------------------------------------------------
+ * Validation depth metrics (main.py:565-593 and evaluate_metric,
+ * main.py:727-747 with demon_metrics.py:63 l1_inverse, :130 scale_invariant)
+ * ------------------------------------------------------------------------ */
+/* Scratch for sfm_depth_metrics: selection state, radix histograms and the
+ * per-chunk partial sums (0 for an invalid shape). */
+size_t sfm_depth_metrics_workspace_bytes(int batch, int H, int W);
+
+/* One row of sums per pair, replacing the per-pair loop of main.py:565-593
+ * (mask, median scale, clamp) and evaluate_metric's numpy reductions
+ * (main.py:727-747), stream-ordered and without a host synchronisation:
+ *   pred [dev] float32, pair b's pixel (y, x) at pred[b * pred_batch_stride +
+ *     y * pred_row_stride + x]: the top-left H x W crop of the padded
+ *     prediction is read in place (main.py:495-499, 543);
+ *   gt [dev] batch x H x W float32;
+ *   rescale [dev] batch float32 or NULL: p0 = pred * rescale[b] (main.py:536-541);
+ *   mask_mode 0 (KITTI, main.py:568-574): gt > 0 && gt < 80 inside
+ *     [y0, y1) x [x0, x1), the Eigen crop the host computes;
+ *   mask_mode 1 (DeMoN, main.py:566): 0.5 <= gt <= 10; the rectangle is ignored;
+ *   scale = median(gt[mask]) / median(p0[mask]) with torch's lower median,
+ *     over the whole image when the mask is empty (main.py:580-582);
+ *   p = p0 * scale, p <= min_depth -> min_depth, p > max_depth -> max_depth
+ *     (main.py:588-590; max_depth = MIN_DEPTH * nlabel);
+ *   rows [dev] batch x 16 float64: 0 n, 1 med_gt, 2 med_p, 3 scale, then over
+ *     the masked pixels with d = gt - p: 4 sum |d|/gt, 5 sum d*d/gt, 6 sum d*d,
+ *     7 sum l*l, 8 sum l (l = log gt - log p, float64), 9-11 the counts of
+ *     max(gt/p, p/gt) < 1.25, 1.25^2, 1.25^3, 12 sum |1/gt - 1/p|, 13-15 zero.
+ *     Terms are formed in float32 as numpy forms them and summed in float64 in
+ *     a fixed order: a pair's row does not depend on the batch around it;
+ *   depth_out [dev] batch x H x W float32 (p at every pixel) or NULL. */
+int sfm_depth_metrics(const float* pred, int64_t pred_batch_stride, int pred_row_stride,
+                      const float* gt, int batch, int H, int W, const float* rescale,
+                      int mask_mode, int y0, int y1, int x0, int x1,
+                      float min_depth, float max_depth,
+                      double* rows, float* depth_out,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* 3-D cost regularisation layer of PSNet (models/PSNet.py:79-102, applied at
  * PSNet.py:159-165; convbn_3d = Conv3d(3, stride 1, pad 1, no bias) +
  * BatchNorm3d, models/submodule.py:17-20), on the matrix cores in bf16 with
@@ -558,7 +595,8 @@ int sfm_profile_select(const char* names);
 int sfm_profile_reset(void);
 /* Synchronises the recorded events; total milliseconds and launch count of
  * kernel `name` ("ransac_solve", "ransac_chain", "ransac_score",
- * "ransac_select", "flow_to_points", "plane_sweep", "sweep_tgt_quads", ...). */
+ * "ransac_select", "flow_to_points", "plane_sweep", "sweep_tgt_quads",
+ * "depth_metrics", ...). */
 int sfm_profile_read(const char* name, double* total_ms, int* launches);
 
 #ifdef __cplusplus

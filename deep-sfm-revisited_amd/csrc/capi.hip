@@ -135,8 +135,17 @@ const TuneKey kTuneKeys[] = {
     {"score_precision", &sfm::Tuning::score_precision, [](int v) { return v == 64 || v == 32 || v == 16; }},
     {"score_lowp_template", &sfm::Tuning::score_lowp_template, v_01},
 };
+// Switches that sfm_tune_set / sfm_tune_get take but sfm_tune_key does not
+// enumerate: the enumerated set is the launch-shape and scoring knobs the
+// header's "Tuning knobs" block documents one for one (tests/test_abi.py),
+// and these select which call writes an output, not how a kernel runs.
+const TuneKey kSwitchKeys[] = {
+    {"score_ref_rider", &sfm::Tuning::score_ref_rider, v_01},
+};
 const TuneKey* find_key(const char* key) {
   for (const TuneKey& k : kTuneKeys)
+    if (std::string(key) == k.name) return &k;
+  for (const TuneKey& k : kSwitchKeys)
     if (std::string(key) == k.name) return &k;
   return nullptr;
 }

@@ -50,8 +50,35 @@ struct Tuning {
   int score_lowp_template = 0;   // 32 / 16: 0 = E and every operation held in T (this build's variant);
                                  // 1 = the literal ComputeError<T> with double Ematrix (double products)
   int conv_rolling = 1;          // 1: cin-32 conv layers roll along the planes (k_conv3r); 0: k_conv3
+  int score_ref_rider = 1;       // the cost volume's reference half written by the one-sided scorer's first
+                                 // launch (sfm_score_ref_job; score_mf2.h); 0: the sweep writes both halves
 };
 Tuning& tuning();
+
+// Uniform integer division by a host-made magic number (the sweep's window
+// decode, the scorer's store rider).
+struct Magic {   // floor(n / d) = (n * m) >> s for 0 <= n < 2^31
+  unsigned m, s;
+};
+inline Magic make_magic(unsigned d) {
+  unsigned l = 0;
+  while ((1ull << l) < d) ++l;
+  const unsigned long long two = 1ull << (31 + l);
+  return Magic{(unsigned)((two + d - 1) / d), 31 + l};
+}
+__device__ __forceinline__ unsigned magic_div(unsigned n, Magic mg) {
+  return (unsigned)(((unsigned long long)n * mg.m) >> mg.s);
+}
+
+// The reference half of a cost volume that a RANSAC call writes from inside
+// its scorer (sfm_score_ref_job): ref [B*C][hw] float32 -> cost [B][2C][L][hw].
+struct RefJob {
+  const float* ref = nullptr;
+  void* cost = nullptr;
+  int batch = 0, channels = 0, nlabel = 0, h = 0, w = 0, dtype = 0;
+};
+// the job armed for stream s, if any, disarmed (ransac5.hip)
+bool take_ref_job(hipStream_t s, RefJob* job);
 
 // The score kernel the last RANSAC / score call dispatched (sfm_last_scorer):
 // a static string literal.

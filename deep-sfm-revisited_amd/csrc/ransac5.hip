@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <mutex>
 #include <vector>
+#include <hip/hip_bf16.h>
 #include "common.h"
 #include "five_point.h"
 
@@ -1525,6 +1526,39 @@ __global__ void k_keypoint_points(const float* __restrict__ flow, int H, int W, 
 #include "score_mf.h"
 #include "score_mf2.h"
 
+// The rider's launch parameters for a job, or false when the shape is outside
+// its fast path (the caller then writes the reference half with
+// sfm_plane_sweep_ref_planes): rows of even length whose periods start
+// 16-byte aligned, 32-bit slab offsets, piece and run counts below 2^31.
+template <int kFmt>
+static bool make_rider(const RefJob& j, long long max_runs, RefRider<kFmt>* r) {
+  const long long hw = (long long)j.h * j.w, L = j.nlabel;
+  const long long esz = kFmt == 1 ? 4 : 2;
+  if (hw < 4 || hw % 2 != 0 || (hw % 4 != 0 && L % 2 != 0)) return false;
+  const long long P = hw % 4 == 0 ? hw : 2 * hw, np = L * hw / P;
+  const long long slab_bytes = L * hw * esz;
+  if (slab_bytes >= (1ll << 32) || (uintptr_t)j.ref % 8 != 0 || (uintptr_t)j.cost % 16 != 0) return false;
+  const long long rows = (long long)j.batch * j.channels;
+  const long long cpp = (P + 255) / 256, gpp = (np + kRiderStores - 1) / kRiderStores;
+  const long long T = rows * cpp * gpp;
+  if (T >= (1ll << 31) || max_runs >= (1ll << 31)) return false;
+  r->ref = j.ref;
+  r->cost = j.cost;
+  r->T = (unsigned)T;
+  r->C = (unsigned)j.channels;
+  r->hw = (unsigned)hw;
+  r->P = (unsigned)P;
+  r->cpp = (unsigned)cpp;
+  r->np = (unsigned)np;
+  r->gpp = (unsigned)gpp;
+  r->slab_bytes = (unsigned)slab_bytes;
+  r->mcpp = make_magic((unsigned)cpp);
+  r->mgpp = make_magic((unsigned)gpp);
+  r->mC = make_magic((unsigned)j.channels);
+  return true;
+}
+
+
 // The score-kernel choice (shared by the RANSAC driver and
 // sfm_score_essentials): the split-f16 matrix-core scorers when the threshold
 // and precision allow, else the float32 / float64 VALU scorers.
@@ -1552,7 +1586,8 @@ static int lowp_prec() {
 template <class Src>
 static void score_dispatch(const Src& src, const PairParams& pp, int bc, int cmax, const ScoreBufs& w,
                            const ScoreConsts& kc, const MfParams& mp, bool use_mf, bool same, int prec, bool fast,
-                           bool fast32, int cus, int grid, hipStream_t s, int prune_pm = 0) {
+                           bool fast32, int cus, int grid, hipStream_t s, int prune_pm = 0,
+                           const RefJob* ref_job = nullptr, bool* rode = nullptr) {
   if (use_mf) {
     hipLaunchKernelGGL(k_mf_cands, dim3((cmax + 255) / 256, bc), dim3(256), 0, s, cmax, w.cand_total, w.candE,
                        w.candF, mp, w.claim, prune_pm > 0 ? w.lead : nullptr);
@@ -1578,9 +1613,29 @@ static void score_dispatch(const Src& src, const PairParams& pp, int bc, int cma
         //   their counts zeroed, then counted exactly: float64 (k_mf2_exact)
         //   for pairs with at most score_mf_exact_max of them, the two-sided
         //   matrix-core pass through the index map for the others (lead row 4)
-        hipLaunchKernelGGL((k_score_mf2<Src, false, true>), g2, b2u, 0, s, src, pp, bc, cmax, w.cand_total, w.candE,
-                           w.candF, w.cntT, kc, w.claim, (const int32_t*)nullptr, 0, prune_pm,
-                           (const int32_t*)nullptr, 0, ch);
+        // (with a reference-half job inside the rider's fast path, A also
+        // writes that half: the store rider of score_mf2.h)
+        long long max_runs = 0;
+        for (int b = 0; b < bc; ++b)
+          max_runs += (long long)mf2_spans(std::max(pp.test[b], pp.rtest[b])) * ((cmax + kKC - 1) / kKC);
+        RefRider<1> r32;
+        RefRider<2> r16;
+        if (ref_job && tuning().score_ref_rider && ref_job->dtype == 0 && make_rider(*ref_job, max_runs, &r32)) {
+          hipLaunchKernelGGL((k_score_mf2<Src, false, true, RefRider<1>>), g2, b2u, 0, s, src, pp, bc, cmax,
+                             w.cand_total, w.candE, w.candF, w.cntT, kc, w.claim, (const int32_t*)nullptr, 0,
+                             prune_pm, (const int32_t*)nullptr, 0, ch, r32);
+          *rode = true;
+        } else if (ref_job && tuning().score_ref_rider && ref_job->dtype == 1 &&
+                   make_rider(*ref_job, max_runs, &r16)) {
+          hipLaunchKernelGGL((k_score_mf2<Src, false, true, RefRider<2>>), g2, b2u, 0, s, src, pp, bc, cmax,
+                             w.cand_total, w.candE, w.candF, w.cntT, kc, w.claim, (const int32_t*)nullptr, 0,
+                             prune_pm, (const int32_t*)nullptr, 0, ch, r16);
+          *rode = true;
+        } else {
+          hipLaunchKernelGGL((k_score_mf2<Src, false, true>), g2, b2u, 0, s, src, pp, bc, cmax, w.cand_total,
+                             w.candE, w.candF, w.cntT, kc, w.claim, (const int32_t*)nullptr, 0, prune_pm,
+                             (const int32_t*)nullptr, 0, ch);
+        }
         hipLaunchKernelGGL(k_mf2_split, dim3(bc), dim3(1024), 0, s, pp, cmax, prune_pm,
                            tuning().score_mf_prune_margin, w.cand_total, w.cntT, w.bnd, w.lead);
         hipLaunchKernelGGL((k_score_mf2<Src, false, true>), g2, b2u, 0, s, src, pp, bc, cmax, w.cand_total, w.candE,
@@ -1824,11 +1879,71 @@ static int wait_score_gate(hipStream_t s) {
   return SFM_OK;
 }
 
+// Reference-half jobs (sfm_score_ref_job): one slot per (device, stream), the
+// job handed to the next RANSAC call issued on that stream, which consumes it
+// whatever path it takes.  A slot holds no HIP object and nothing waits on it:
+// arming again for a stream replaces its job, a job for a stream that never
+// issues another RANSAC call is overwritten by the oldest-first reuse of the
+// slots (it cannot exhaust them), and calls on other streams never see it.
+constexpr int kRefJobs = 32;
+struct RefJobSlot {
+  int dev = -1;                  // -1: free
+  hipStream_t stream = nullptr;
+  unsigned long long seq = 0;    // arming order (the oldest slot is reused first)
+  RefJob job;
+};
+static RefJobSlot g_ref_jobs[kRefJobs];
+static unsigned long long g_ref_seq = 0;
+static int g_ref_armed = 0;      // armed slots (g_fence_mu)
+
+bool take_ref_job(hipStream_t s, RefJob* job) {
+  std::lock_guard<std::mutex> lk(g_fence_mu);
+  if (g_ref_armed == 0) return false;
+  int dev = 0;
+  if (stream_device(s, &dev)) return false;
+  for (RefJobSlot& j : g_ref_jobs)
+    if (j.dev == dev && j.stream == s) {
+      *job = j.job;
+      j.dev = -1;
+      --g_ref_armed;
+      return true;
+    }
+  return false;
+}
+
+// 0 / 1: the armed jobs (tests: nothing accumulates)
+static int arm_ref_job(hipStream_t s, const RefJob* job) {
+  std::lock_guard<std::mutex> lk(g_fence_mu);
+  int dev = 0;
+  if (int rc = stream_device(s, &dev)) return rc;
+  RefJobSlot* slot = nullptr;
+  for (RefJobSlot& j : g_ref_jobs)
+    if (j.dev == dev && j.stream == s) slot = &j;
+  if (!job) {
+    if (slot) {
+      slot->dev = -1;
+      --g_ref_armed;
+    }
+    return SFM_OK;
+  }
+  if (!slot) {
+    for (RefJobSlot& j : g_ref_jobs)                         // a free slot, else the oldest armed one
+      if (!slot || (slot->dev >= 0 && (j.dev < 0 || j.seq < slot->seq))) slot = &j;
+    if (slot->dev < 0) ++g_ref_armed;
+  }
+  slot->dev = dev;
+  slot->stream = s;
+  slot->seq = ++g_ref_seq;
+  slot->job = *job;
+  return SFM_OK;
+}
+
 template <class Src>
 static int run_chunk(const Src& src, const int64_t* n, int bc, int num_test,
                      int num_ransac_test, int iters, double thr, uint64_t seed, int cheir,
                      const Workspace& w, int ws_batch, double* E_out, double* P_out, int32_t* inliers_out,
-                     int32_t* winner_out, int32_t* score_out, hipStream_t s, bool first_chunk) {
+                     int32_t* winner_out, int32_t* score_out, hipStream_t s, bool first_chunk,
+                     const RefJob* ref_job = nullptr, bool* rode = nullptr) {
   const int H = kChains * iters;
   const int cmax = H * kMaxSlots;
   PairParams pp{};
@@ -1922,7 +2037,8 @@ static int run_chunk(const Src& src, const int64_t* n, int bc, int num_test,
     sb.lead = w.lead;
     sb.bnd = w.bnd;
     sb.skipped = w.skipped;
-    score_dispatch(src, pp, bc, cmax, sb, kc, mp, use_mf, same, prec, fast, fast32, cus, grid, s, mf2_pm);
+    score_dispatch(src, pp, bc, cmax, sb, kc, mp, use_mf, same, prec, fast, fast32, cus, grid, s, mf2_pm, ref_job,
+                   rode);
   }
   SFM_LAUNCHED();
   {
@@ -1957,13 +2073,25 @@ static int run_src(const Src& src, const int64_t* n, int batch, int num_test, in
   Workspace w;
   layout((char*)ws, bc, 0, iters, &w);
   const int H = kChains * iters;
+  // a reference-half job armed for this stream (sfm_score_ref_job): consumed
+  // here; the first chunk's scorer writes it when its first launch is the
+  // one-sided pass and the shape is in the rider's range, else the reference
+  // kernels do, on this stream, before the call returns
+  RefJob job;
+  const bool have_job = take_ref_job(s, &job);
+  bool rode = false;
   for (int b0 = 0; b0 < batch; b0 += bc) {
     const int nb = std::min(bc, batch - b0);
-    if (int rc = run_chunk(src.shifted(b0), n + b0, nb, num_test, num_ransac_test, iters, thr, seed, cheir, w, bc,
-                           E_out + (size_t)b0 * 9, P_out ? P_out + (size_t)b0 * 12 : nullptr, inliers_out + b0,
-                           winner_out ? winner_out + b0 : nullptr,
-                           score_out ? score_out + (size_t)b0 * H : nullptr, s, b0 == 0))
-      return rc;
+    const int rc = run_chunk(src.shifted(b0), n + b0, nb, num_test, num_ransac_test, iters, thr, seed, cheir, w, bc,
+                             E_out + (size_t)b0 * 9, P_out ? P_out + (size_t)b0 * 12 : nullptr, inliers_out + b0,
+                             winner_out ? winner_out + b0 : nullptr,
+                             score_out ? score_out + (size_t)b0 * H : nullptr, s, b0 == 0,
+                             have_job && b0 == 0 ? &job : nullptr, &rode);
+    if (have_job && b0 == 0 && !rode)
+      if (int rc2 = sfm_plane_sweep_ref_planes(job.ref, job.batch, job.channels, job.h, job.w, job.nlabel, job.dtype,
+                                               job.cost, nullptr, 0, s))
+        return rc2;
+    if (rc) return rc;
   }
   return SFM_OK;
 }
@@ -2099,6 +2227,27 @@ int sfm_score_gate(void* stream, void* waiter, int arm) {
   slot->waiter = (hipStream_t)waiter;
   slot->armed = true;
   return SFM_OK;
+}
+
+int sfm_score_ref_job(void* stream, const float* ref, void* cost, int batch, int channels, int nlabel, int h, int w,
+                      int cost_dtype) {
+  if (!ref && !cost) return arm_ref_job((hipStream_t)stream, nullptr);   // disarm
+  SFM_REQUIRE(ref && cost, "null pointer argument");
+  // (the limits of sfm_plane_sweep_ref_planes, which writes the job when the scorer cannot)
+  SFM_REQUIRE(batch >= 1 && batch <= 65535 && channels >= 1 && channels <= 65535 && h >= 1 && w >= 1 && nlabel >= 1,
+              "invalid sweep shape");
+  SFM_REQUIRE((int64_t)batch * channels <= 65535, "batch * channels must be <= 65535");
+  SFM_REQUIRE((int64_t)h * w < ((int64_t)1 << 30), "feature map too large");
+  SFM_REQUIRE(cost_dtype == 0 || cost_dtype == 1, "cost_dtype must be 0 (float32) or 1 (bfloat16)");
+  RefJob j;
+  j.ref = ref; j.cost = cost; j.batch = batch; j.channels = channels; j.nlabel = nlabel; j.h = h; j.w = w;
+  j.dtype = cost_dtype;
+  return arm_ref_job((hipStream_t)stream, &j);
+}
+
+int sfm_score_ref_jobs_armed(void) {
+  std::lock_guard<std::mutex> lk(g_fence_mu);
+  return g_ref_armed;
 }
 
 size_t sfm_score_essentials_workspace_bytes(int batch, int ncand) {

@@ -175,17 +175,130 @@ __device__ __forceinline__ int32_t* mf2_count_slot(int32_t* cntT, const int32_t*
   return cntT + (size_t)b * cmax + (cmap ? cmap[i] : j);
 }
 
+// The store rider (sfm_score_ref_job): the first launch of the one-sided
+// pruning also writes the reference half of a cost volume, cost[b][c][l] =
+// ref[b][c] for every plane l (PSNet.py:155) -- 3.86 GB of pose-independent
+// broadcast at the KITTI bench shape, written while the scorer, bound by VALU
+// issue, leaves HBM idle, so that the sweep after RANSAC writes the warped
+// half alone.  The scorer's own waves issue the stores at their run
+// boundaries (a run: one wave, one 32-candidate tile, one span), where the
+// tile loop's registers are dead; the tile loop is untouched.
+//
+// Layout.  A slab (pair b, channel c) is L * hw contiguous elements, its
+// value at element e is ref[b][c][e mod hw].  It is cut into np periods of P
+// elements, P = hw (hw % 4 == 0) or 2 hw (hw % 4 == 2 with L even), so every
+// period starts 16-byte aligned, and a period into chunks of 256 elements (4
+// per lane: a 1-KB wave store in float32).  A piece is (slab, chunk, group of
+// kRiderStores periods): the lane reads its 16 bytes of the row once and
+// stores them to the group's periods with the sweep's cache policy (float32
+// nt sc1, bfloat16 sc0 nt; bfloat16 by the sweep's RNE conversion, once).
+//
+// Schedule.  The launch has U runs, known on the device, and the job T
+// pieces.  Run ug writes pieces [at(ug), at(ug + 1)), at(x) = x q + (x f >>
+// 32) with q = T / U and f = floor((T mod U) 2^32 / U), and the last run up to
+// T: every run happens exactly once, so every piece is written exactly once,
+// spread evenly over the launch, without a counter or a drain -- a copy
+// longer than the scorer just puts more pieces into each run.  With no run
+// at all (no candidate anywhere) the blocks share the pieces and leave.
+//
+// The first piece of a run loads its source under the run's reduction and
+// stores after it, behind an explicit wait for the loads issued so far (the
+// source and the next run's A rows), so that nothing later waits on the
+// stores' own completion; only further pieces of the same run (the
+// copy-bound case) wait for the stores before them.
+constexpr int kRiderStores = 8;                // periods a piece writes
+struct RiderNone {};
+template <int kFmt>                            // 1: float32 volume, 2: bfloat16
+struct RefRider {
+  static constexpr int fmt = kFmt;
+  const float* ref;                            // [rows][hw]
+  void* cost;                                  // [B][2C][L][hw]
+  unsigned T;                                  // pieces
+  unsigned C, hw, P, cpp, np, gpp;             // channels; chunks per period, periods, period groups per slab
+  unsigned slab_bytes;                         // L * hw elements of the volume
+  Magic mcpp, mgpp, mC;
+};
+template <class R> __device__ __forceinline__ const R& rider_of(const R& r) { return r; }
+
+struct RiderPiece {                            // a lane's part of a piece
+  float2 a, b;                                 // 4 consecutive elements of the row (period element x ..)
+  bool live;                                   // x < P
+};
+// uniform decode of piece p: the slab's first byte, the lane-independent part
+template <class R>
+__device__ __forceinline__ void rider_decode(const R& rj, unsigned p, unsigned& row, unsigned& j, unsigned& pg) {
+  const unsigned t = magic_div(p, rj.mcpp);
+  j = p - t * rj.cpp;
+  row = magic_div(t, rj.mgpp);
+  pg = t - row * rj.gpp;
+}
+template <class R>
+__device__ __forceinline__ RiderPiece rider_load(const R& rj, unsigned p, int lane) {
+  unsigned row, j, pg;
+  rider_decode(rj, p, row, j, pg);
+  const unsigned x = 256u * j + 4u * (unsigned)lane;
+  RiderPiece d;
+  d.live = x < rj.P;
+  d.a = float2{0.0f, 0.0f};
+  d.b = float2{0.0f, 0.0f};
+  if (d.live) {
+    // hw is even: an aligned pair of the period never straddles the row's end
+    const float* src = rj.ref + (size_t)row * rj.hw;
+    const unsigned s0 = x >= rj.hw ? x - rj.hw : x, s1 = x + 2u >= rj.hw ? x + 2u - rj.hw : x + 2u;
+    d.a = *reinterpret_cast<const float2*>(src + s0);
+    d.b = *reinterpret_cast<const float2*>(src + s1);
+  }
+  return d;
+}
+__device__ __forceinline__ unsigned rider_bf16(float v) {   // to_bf16 of warp.h: round to nearest even
+  __hip_bfloat16 h = __float2bfloat16(v);
+  return (unsigned)*reinterpret_cast<unsigned short*>(&h);
+}
+template <class R>
+__device__ __forceinline__ void rider_store(const R& rj, unsigned p, int lane, const RiderPiece& d) {
+  unsigned row, j, pg;
+  rider_decode(rj, p, row, j, pg);
+  const unsigned b = magic_div(row, rj.mC), c = row - b * rj.C;
+  constexpr unsigned esz = R::fmt == 1 ? 4u : 2u;
+  char* slab = (char*)rj.cost + ((size_t)b * 2u * rj.C + c) * (size_t)rj.slab_bytes;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(slab, 0, (int)rj.slab_bytes, 0x00020000);
+  const unsigned n0 = pg * (unsigned)kRiderStores, n1 = min(rj.np, n0 + (unsigned)kRiderStores);
+  const unsigned step = rj.P * esz;
+  unsigned voff = (n0 * rj.P + 256u * j + 4u * (unsigned)lane) * esz;
+  if (!d.live) return;
+  // (a literal-0 soffset: the 128-bit stores' data hazard, sweep.hip)
+  if constexpr (R::fmt == 1) {
+    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+    const u32x4_t v = {__float_as_uint(d.a.x), __float_as_uint(d.a.y), __float_as_uint(d.b.x), __float_as_uint(d.b.y)};
+#pragma unroll 1
+    for (unsigned n = n0; n < n1; ++n, voff += step) __builtin_amdgcn_raw_buffer_store_b128(v, rs, voff, 0, 18);
+  } else {
+    typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+    const u32x2_t v = {rider_bf16(d.a.x) | (rider_bf16(d.a.y) << 16), rider_bf16(d.b.x) | (rider_bf16(d.b.y) << 16)};
+#pragma unroll 1
+    for (unsigned n = n0; n < n1; ++n, voff += step) __builtin_amdgcn_raw_buffer_store_b64(v, rs, voff, 0, 3);
+  }
+}
+// at(x): the first piece of run x
+__device__ __forceinline__ unsigned rider_at(unsigned x, unsigned q, unsigned f) {
+  return x * q + (unsigned)(((unsigned long long)x * f) >> 32);
+}
+
 // kUpper (round 6): the one-sided pass of count-bound pruning -- z2 only (3
 // MFMAs and 32 VALU per tile instead of 4 and 48), each count the number of
 // points NOT certainly outliers (sign of z2), an upper bound on the inlier
 // count; no undecided queue, no float64 drain.
-template <class Src, bool kMap, bool kUpper = false>
+// Rider: nothing, or one RefRider (the store rider above; a trailing kernel
+// argument that the other instantiations do not have).
+template <class Src, bool kMap, bool kUpper = false, class... Rider>
 __global__ __launch_bounds__(mf2_waves<kUpper>() * 64)
 __attribute__((amdgpu_waves_per_eu(mf2_waves<kUpper>() / 4, mf2_waves<kUpper>() / 4))) void k_score_mf2(
     const Src src, PairParams pp, int batch, int cmax, const int32_t* __restrict__ cand_total,
     const double* __restrict__ candE, const _Float16* __restrict__ candF, int32_t* __restrict__ cntT,
     ScoreConsts kc, unsigned long long* __restrict__ claim, const int32_t* __restrict__ cmap_arg, int sp_lo,
-    int sp_hi, const int32_t* __restrict__ bnd, int phase, int min_chunk) {
+    int sp_hi, const int32_t* __restrict__ bnd, int phase, int min_chunk, const Rider... rider) {
+  constexpr bool kRide = sizeof...(Rider) > 0;
+  static_assert(sizeof...(Rider) <= 1, "one rider");
   // one count array: this kernel runs only when num_test == num_ransac_test,
   // so the preselection count is the score and k_select reads cntT for both
   __shared__ __attribute__((aligned(16))) _Float16 s_frag[kMf2Tiles][3][64][8];
@@ -200,6 +313,7 @@ __attribute__((amdgpu_waves_per_eu(mf2_waves<kUpper>() / 4, mf2_waves<kUpper>() 
   __shared__ int32_t s_span0[SFM_MAX_BATCH];                 // the pair's first span in this launch
   __shared__ int32_t s_claim;                                // next candidate tile of the span to claim
   __shared__ long long s_range[2];                           // the block's current unit range
+  __shared__ uint32_t s_ride[kRide ? 2 : 1];                 // the rider's pieces per run (q, f)
   // the compacted candidates' index map: a compile-time null in the launches
   // without one, so that its address arithmetic costs the tile loop no registers
   const int32_t* __restrict__ const cmap = kMap ? cmap_arg : nullptr;
@@ -221,11 +335,26 @@ __attribute__((amdgpu_waves_per_eu(mf2_waves<kUpper>() / 4, mf2_waves<kUpper>() 
       acc += (long long)(s1 - s0) * tiles;
     }
     s_first[batch] = acc;
+    if constexpr (kRide) {
+      // the rider's rate: pieces per run as q + f / 2^32 (U < 2^31 by the host's bound)
+      const unsigned T = rider_of(rider...).T;
+      const unsigned long long Uu = (unsigned long long)acc;
+      s_ride[0] = Uu ? (unsigned)(T / Uu) : 0u;
+      s_ride[1] = Uu ? (unsigned)(((T % Uu) << 32) / Uu) : 0u;
+    }
   }
   __syncthreads();
   // nothing to score (the one-sided pruning's matrix-core pass when every
   // pair's kept candidates went to k_mf2_exact): out before the table set-up.
   // No block claims a unit, so the counters stay as the last launch left them.
+  if constexpr (kRide) {
+    if (s_first[batch] == 0) {                               // no run to ride on: the launch's waves share the pieces
+      const auto& rj = rider_of(rider...);
+      const int lane = mf2_lane();
+      for (unsigned p = blockIdx.x * (unsigned)NW + (unsigned)wv; p < rj.T; p += gridDim.x * (unsigned)NW)
+        rider_store(rj, p, lane, rider_load(rj, p, lane));
+    }
+  }
   if (s_first[batch] == 0) return;
   for (int i = tid; i < (kUpper ? 1 : NW) * kKC; i += NW * 64) (&s_cnt[0][0])[i] = 0;
   for (int i = tid; i < kMf2TblWords; i += NW * 64) s_tbl[i] = 0;
@@ -355,6 +484,9 @@ __attribute__((amdgpu_waves_per_eu(mf2_waves<kUpper>() / 4, mf2_waves<kUpper>() 
       int k = claim_tile();
       const int ctot = __builtin_amdgcn_readfirstlane(s_ctot[b]);   // the pair's candidates, in an SGPR
       if (k < k1) load_rows(b, k, ctot);
+      // (the rider: the rows are awaited here, as after every run, so that the
+      // tile loop's head has no load to wait for and passes pending stores)
+      if constexpr (kRide) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
 #pragma unroll 1
       while (k < k1) {
         const int c0 = k * kKC;
@@ -407,6 +539,18 @@ __attribute__((amdgpu_waves_per_eu(mf2_waves<kUpper>() / 4, mf2_waves<kUpper>() 
           zB = mf2_z(mf2_load_d(fr + (size_t)(kMf2Tiles - 1) * kTileHalves, mf2_lane()), NL, NH, aB);
           mf2_signs(zA, s1, s2);
           mf2_signs(zB, s1, s2);
+        }
+        // the rider's pieces of this run; the first one's source loads here
+        unsigned rp = 0u, rp_end = 0u;
+        RiderPiece rd{};
+        if constexpr (kRide) {
+          // (uniform values made scalar first, so that the schedule is SALU work)
+          const unsigned ug = __builtin_amdgcn_readfirstlane((unsigned)u) + (unsigned)(k - k0);
+          const unsigned rq = __builtin_amdgcn_readfirstlane(s_ride[0]), rf = __builtin_amdgcn_readfirstlane(s_ride[1]);
+          rp = rider_at(ug, rq, rf);
+          rp_end = ug + 1u == __builtin_amdgcn_readfirstlane((unsigned)U) ? rider_of(rider...).T
+                                                                          : rider_at(ug + 1u, rq, rf);
+          if (rp < rp_end) rd = rider_load(rider_of(rider...), rp, mf2_lane());
         }
         const int lane = mf2_lane(), hl = lane >> 5, rl = lane & 31;
         // the next run's rows load under this run's queue, drain and reduction
@@ -512,6 +656,17 @@ __attribute__((amdgpu_waves_per_eu(mf2_waves<kUpper>() / 4, mf2_waves<kUpper>() 
           }
         }
         wave_sync();
+        if constexpr (kRide) {
+          // every load so far has landed (the source, the next run's rows, which
+          // the tile loop needs next in any case): on every path, so that
+          // nothing after this point waits on the stores that follow
+          __builtin_amdgcn_s_waitcnt(0x0F70);                 // vmcnt(0)
+          if (rp < rp_end) {
+            const auto& rj = rider_of(rider...);
+            rider_store(rj, rp, lane, rd);
+            for (unsigned p = rp + 1u; p < rp_end; ++p) rider_store(rj, p, lane, rider_load(rj, p, lane));
+          }
+        }
         k = kn;
       }
       u += k1 - k0;

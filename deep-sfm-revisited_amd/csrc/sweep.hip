@@ -357,18 +357,7 @@ __global__ __launch_bounds__(kSwThreads) void k_sweep(const float* __restrict__ 
 // ---------------------------------------------------------------------------
 constexpr int kFlatWin = 1024;
 
-struct Magic {   // floor(n / d) = (n * m) >> s for 0 <= n < 2^31
-  unsigned m, s;
-};
-static Magic make_magic(unsigned d) {
-  unsigned l = 0;
-  while ((1ull << l) < d) ++l;
-  const unsigned long long two = 1ull << (31 + l);
-  return Magic{(unsigned)((two + d - 1) / d), 31 + l};
-}
-__device__ __forceinline__ unsigned magic_div(unsigned n, Magic mg) {
-  return (unsigned)(((unsigned long long)n * mg.m) >> mg.s);
-}
+// (Magic / make_magic / magic_div: common.h)
 
 struct FlatGeom {
   int B, C, C4, h, w, L, hw;

@@ -55,6 +55,9 @@ _SIGS = [
     ("sfm_score_fence_enable", ctypes.c_int, [ctypes.c_int]),
     ("sfm_score_fence_wait", ctypes.c_int, [_c_dp]),
     ("sfm_score_gate", ctypes.c_int, [_c_dp, _c_dp, ctypes.c_int]),
+    ("sfm_score_ref_job", ctypes.c_int,
+     [_c_dp, _c_dp, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    ("sfm_score_ref_jobs_armed", ctypes.c_int, []),
     ("sfm_plane_sweep_ref_planes_workspace_bytes", ctypes.c_size_t,
      [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     ("sfm_plane_sweep_ref_planes", ctypes.c_int,

@@ -181,6 +181,28 @@ class TwoViewHotPath:
         if self.overlap_ref:
             return self.step_overlap(flow, K, ref_fea, tgt_fea)
         Kinv = self.k_inverse(K)
+        if self.ref_rider():
+            # the reference half rides on the RANSAC scorer's first launch, which
+            # leaves HBM idle (sfm_score_ref_job; csrc/score_mf2.h): armed for
+            # this stream, consumed by the pose stage, same stream throughout;
+            # the sweep then writes the warped half alone.  The same volume.
+            ref = ref_fea.contiguous().float()
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.load().sfm_score_ref_job(
+                    _lib.stream_ptr(self.device), _lib.ptr(ref), _lib.ptr(self.cost), self.batch, self.C, self.L,
+                    self.h, self.w, 0 if self.cost_dtype == torch.float32 else 1), "sfm_score_ref_job")
+            E, P, inl, win = self.pose(flow, K, Kinv)
+            cost = sweep.plane_sweep_cost_psnet(ref, tgt_fea, P, K, Kinv, self.L, self.min_depth, self.rescale,
+                                                self.cost_dtype, out=self.cost, workspace=self.sweep_ws,
+                                                warped_half=True)
+            return E, P, inl, cost
         E, P, inl, win = self.pose(flow, K, Kinv)
         cost = self.sweep(ref_fea, tgt_fea, P, K, Kinv)
         return E, P, inl, cost
+
+    def ref_rider(self):
+        """Whether ``step`` hands the volume's reference half to the RANSAC
+        call: the switch ``score_ref_rider`` is on and the pose stage's scorer
+        is the one the rider lives in (dense pairs of at least 32 spans of
+        1024 points); other shapes keep the one-launch sweep."""
+        return self.kp is None and self.n > 31 * 1024 and _lib.tune_get("score_ref_rider") == 1

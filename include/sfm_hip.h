@@ -294,6 +294,35 @@ int sfm_score_fence_wait(void* stream);
  * counterpart: the reference's steps are serial (essential_matrix.cu:190-280
  * then PSNet.py:130-158). */
 int sfm_score_gate(void* stream, void* waiter, int arm);
+
+/* Reference-half job.  Arms a one-shot job for the next RANSAC call
+ * (sfm_ransac5 / _packed / _flow) issued on `stream`: that call also writes
+ * the pose-independent reference half of the cost volume `cost` [batch,
+ * 2 * channels, nlabel, h, w] (cost_dtype 0 float32, 1 bfloat16), cost[b, c, l]
+ * = ref[b, c] for every plane l (PSNet.py:155), from `ref` [batch, channels,
+ * h, w] float32 -- the same bytes sfm_plane_sweep_ref_planes writes -- on the
+ * same stream, so that the sweep after it can be the warped half alone
+ * (sfm_plane_sweep_psnet_warped_half).  When the call's scorer is the pruned
+ * matrix-core scorer (dense pairs of >= 32 spans of 1024 points, num_test ==
+ * num_ransac_test, no per-hypothesis scores, "score_mf_prune_upper" = 1) and
+ * h * w is even (with nlabel even when h * w % 4 == 2), ref 8-byte and cost
+ * 16-byte aligned, the scorer's first launch issues the stores from its own
+ * waves while it leaves HBM idle (the store rider, csrc/score_mf2.h); in
+ * every other case, and with the switch "score_ref_rider" (sfm_tune_set; 0,
+ * 1; default 1; not enumerated by sfm_tune_key) at 0, the call runs
+ * sfm_plane_sweep_ref_planes' kernels on the stream instead.  Either way the
+ * half is complete, in stream order, when the call's own outputs are.
+ * The job is scoped to (device, stream): RANSAC calls on other streams
+ * neither see nor consume it.  It is consumed by the next call on the stream
+ * whatever path that call takes; arming again for the stream replaces it;
+ * ref == NULL and cost == NULL disarms.  A slot holds no HIP object and no
+ * call waits on it; of more than 32 armed streams the oldest job is dropped,
+ * so jobs that are never consumed cannot exhaust the slots.  ref and cost
+ * must stay valid until the consuming call's work on the stream is done.
+ * sfm_score_ref_jobs_armed returns the number of armed jobs. */
+int sfm_score_ref_job(void* stream, const float* ref, void* cost, int batch, int channels, int nlabel, int h, int w,
+                      int cost_dtype);
+int sfm_score_ref_jobs_armed(void);
 int sfm_plane_sweep_ref_planes(const float* ref, int batch, int channels, int h, int w, int nlabel, int out_dtype,
                                void* cost, void* workspace, size_t workspace_bytes, void* stream);
 int sfm_plane_sweep_psnet_warped_half(const float* ref, const float* tgt, int batch, int channels, int h, int w,

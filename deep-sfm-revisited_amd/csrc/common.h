@@ -77,8 +77,15 @@ struct RefJob {
   void* cost = nullptr;
   int batch = 0, channels = 0, nlabel = 0, h = 0, w = 0, dtype = 0;
 };
-// the job armed for stream s, if any, disarmed (ransac5.hip)
+// the job armed for stream s, if any, disarmed (score_sync.cpp)
 bool take_ref_job(hipStream_t s, RefJob* job);
+// Stream coordination right before a RANSAC call's scoring phase
+// (score_sync.cpp): record the score fence when enabled; wait for (and
+// consume) the score gate armed for stream s.
+#pragma GCC visibility push(hidden)
+int record_score_fence(hipStream_t s);
+int wait_score_gate(hipStream_t s);
+#pragma GCC visibility pop
 
 // The score kernel the last RANSAC / score call dispatched (sfm_last_scorer):
 // a static string literal.

@@ -1,5 +1,6 @@
-// Phase 3d of the RANSAC (included by ransac5.hip): inlier scoring on the
-// matrix cores with split-f16 operands (k_score_mf, the default scorer).
+// Phase 3 of the RANSAC on the matrix cores (included by ransac_score.hip):
+// inlier scoring with split-f16 operands, item-major (k_score_mf; tuning key
+// score_mf = 1, and the scorer when num_test != num_ransac_test).
 //
 // The Sampson test of ComputeError (kernel_functions.cu:232-264) is, per
 // (candidate E, point), a comparison of two polynomials in the point:
@@ -61,6 +62,11 @@
 // evaluation goes to float64), M <= 15.9 per point (else float64).
 // Numerically emulated before the kernel was written: 0 wrong decisions and
 // 0.65 % undecided over 28M evaluations of 1398 KITTI candidates.
+#pragma once
+#include <cmath>
+#include "score_valu.h"
+
+namespace sfm {
 
 #ifndef SFM_MF_ACC_U
 #define SFM_MF_ACC_U 36
@@ -124,7 +130,6 @@ constexpr int kMfWaves = SFM_MF_WAVES;      // waves per block (3 per SIMD): one
 constexpr int kMfSpan = SFM_MF_SPAN;        // points per item (B fragments staged in LDS)
 constexpr int kMfTiles = kMfSpan / 32;
 constexpr int kMfQueue = 256;               // undecided entries per wave (drained in windows of this size)
-constexpr int kMfRec = 64;                  // f16 per candidate: 4 A rows of K = 16
 constexpr float kMfMaxM = 15.9f;            // M^4 stays below the f16 maximum
 
 // per-candidate A rows (k_mf_cands): a1 [c_hi 0..8, c_hi 0..6] | a2 [c_hi 7..8,
@@ -132,11 +137,8 @@ constexpr float kMfMaxM = 15.9f;            // M^4 stays below the f16 maximum
 // and per-point B columns (staged in k_score_mf) with the same K order:
 // b1 [m_hi 0..8, m_lo 0..6] | b2 [m_lo 7..8, m_hi 0..8, 0 x5] | bD [md 0..10, M^2, (s1/4)^2, (s2/4)^2, 0 x2]
 
-struct MfParams {
-  int k;                 // a' = 2^k a
-  double t_lo, t_hi;     // scaled thresholds thr^2 4^k with the slack factors above
-};
-
+// MfParams (ransac_common.h): a' = 2^k a, and the scaled thresholds thr^2 4^k
+// with the slack factors above
 __host__ inline bool mf_params(double thr, MfParams* p) {
   if (!(thr >= 0x1p-15 && thr < 1.0)) return false;
   int k = 0;
@@ -800,3 +802,5 @@ __global__ __launch_bounds__(kMfWaves * 64) __attribute__((amdgpu_waves_per_eu(S
     for (int i = 0; i < kMfStamps; ++i) atomicAdd(&g_mf_stamps[i], mf_acc_[i]);
 #endif
 }
+
+}  // namespace sfm

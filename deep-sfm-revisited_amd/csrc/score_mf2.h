@@ -1,4 +1,4 @@
-// Phase 3e of the RANSAC (included by ransac5.hip after score_mf.h): the
+// Phase 3 of the RANSAC on the matrix cores (included by ransac_score.hip): the
 // span-major split-f16 matrix-core scorer, k_score_mf2 (default for SFMnet's
 // num_test == num_ransac_test; tuning key score_mf = 2).
 //
@@ -35,7 +35,13 @@
 // A + 12 B + 32 decision strings in the loop.  The round 2-4 schedule and
 // layout variants that measured slower are described in DESIGN_HISTORY.md
 // and the profiles/r0*_mf2_* A/B records; their code is gone.
-constexpr int kMf2Waves = 12;                  // 3 per SIMD, two accumulator sets
+#pragma once
+#include <hip/hip_bf16.h>
+#include "score_mf.h"
+
+namespace sfm {
+
+constexpr int kMf2Waves = 12;                 // 3 per SIMD, two accumulator sets
 constexpr int kMf2Wpe = kMf2Waves / 4;
 // the one-sided pass (kUpper) holds fewer registers (z2 alone): its block
 // size, waves per SIMD = SFM_MF2_UP_WAVES / 4
@@ -43,7 +49,6 @@ constexpr int kMf2Wpe = kMf2Waves / 4;
 #define SFM_MF2_UP_WAVES 16
 #endif
 template <bool kUpper> constexpr int mf2_waves() { return kUpper ? SFM_MF2_UP_WAVES : kMf2Waves; }
-constexpr int kMf2Span = 1024;                 // points per staged span
 constexpr int kMf2Tiles = kMf2Span / 32;       // tiles per span (every run decides all of them)
 constexpr int kMf2Guide = 2;                   // a claim takes remainder / (guide x blocks per XCD)
 constexpr int kMf2Queue = 128;                 // undecided entries per wave and drain window (LDS)
@@ -1015,3 +1020,5 @@ __global__ __launch_bounds__(256) void k_mf2_zero_kept(int cmax, const int32_t* 
   const int j = (int)(blockIdx.x * 256 + threadIdx.x);
   if (j < lead[3 * SFM_MAX_BATCH + b]) cntT[(size_t)b * cmax + cmap[(size_t)b * cmax + j]] = 0;
 }
+
+}  // namespace sfm

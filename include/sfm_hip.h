@@ -171,7 +171,7 @@ int sfm_ransac5_candidate_counts(const void* workspace, size_t workspace_bytes, 
  * and hyp_score_out is NULL), copied to the host (synchronous).  The score
  * kernel performed sum(counts) x max(num_test, num_ransac_test) minus this
  * many evaluations.  Pruning never changes E, P, the inlier count or the
- * winner (ransac5.hip, PruneState). */
+ * winner (ransac_common.h, PruneState). */
 int sfm_ransac5_skipped_evaluations(const void* workspace, size_t workspace_bytes, int batch, int iters,
                                     unsigned long long* skipped_host);
 /* Diagnostics of the last pruned k_score_mf2 call on the workspace

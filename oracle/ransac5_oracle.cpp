@@ -663,7 +663,7 @@ static inline float h16(float f) {
 // half computed in float and rounded once: 24 >= 2*11+2 bits makes the double
 // rounding exact, as for + - *); inputs reach T through float32; the count
 // test against the float64 threshold as at kernel_functions.cu:193-194.
-// Mirrors ransac5.hip:inlier_lowp.
+// Mirrors score_valu.h:inlier_lowp.
 template <int PREC>
 static inline bool is_inlier_lp(const double* E, double xd, double yd, double xpd, double ypd, double thr) {
   auto r = [](float v) { return PREC == 16 ? h16(v) : v; };
@@ -710,7 +710,7 @@ static inline double h16d(double v) {
 // binary16 (prec 17): q, qp converted to T once; `sum += E[k][l] * q[l]` is a
 // double product and a double add, the sum rounded to T; xEx, D, sqrt and the
 // division in T (half: computed in float, rounded once -- exact by the
-// 24 >= 2*11+2 rule); no scaling of E.  Mirrors ransac5.hip:inlier_lowp_tpl.
+// 24 >= 2*11+2 rule); no scaling of E.  Mirrors score_valu.h:inlier_lowp_tpl.
 template <int PREC>
 static inline bool is_inlier_lp_tpl(const double* E, double xd, double yd, double xpd, double ypd, double thr) {
   auto rd = [](double v) { return PREC == 17 ? h16d(v) : (double)(float)v; };     // double -> T

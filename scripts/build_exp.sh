@@ -8,11 +8,12 @@
 set -e
 cd "$(dirname "$0")/../deep-sfm-revisited_amd/csrc"
 mkdir -p ../../scripts/exp
+SRCS=$(make -s print-srcs)   # the Makefile's list: no copy to drift
 build() {
   local name=$1; shift
+  # shellcheck disable=SC2086
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fno-slp-vectorize -fPIC -shared \
-        -I../../include -Wno-unused-result "$@" -o ../../scripts/exp/libsfm_hip_$name.so \
-        capi.hip ransac5.hip sweep.hip depth.hip irls.hip regularize.hip kinv.hip host_polish.cpp
+        -I../../include -Wno-unused-result "$@" -o ../../scripts/exp/libsfm_hip_$name.so $SRCS
 }
 if [ $# -eq 0 ]; then
   build STATS -DSFM_SCORE_STATS

@@ -21,7 +21,9 @@ def kernel_lines(path, sub):
         t = ln.split(";")[0].rstrip()
         if not t.strip() or (t.strip().startswith(".") and not t.strip().endswith(":")):
             continue
-        out.append(t.strip())
+        # block labels carry the function's ordinal within its file (.LBB<fn>_<n>):
+        # dropped, so that a kernel compares equal after moving to another file
+        out.append(re.sub(r"\.LBB\d+_", ".LBB_", t.strip()))
     return out
 
 

@@ -1,6 +1,6 @@
 """Diagnostic: where the RANSAC workspace differs between solve_coop = 0 and 1
 (and between two solve_coop = 0 runs, the determinism check).  Mirrors
-ransac5.hip's layout() for B pairs at iters; prints the differing elements per
+ransac_common.h's layout() for B pairs at iters; prints the differing elements per
 region and, for the solve state, the fields and a few hypotheses' values.
 Usage: solve_coop_diff.py [--sparse]"""
 import os, sys

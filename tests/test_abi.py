@@ -252,6 +252,21 @@ def test_store_hazard_check_sees_vgpr_and_agpr_data():
     assert [h[2].split()[0] for h in hits] == ["v_mov_b32_e32", "v_accvgpr_write_b32", "v_mfma_f32_32x32x16_f16"]
 
 
+def test_makefile_lists_every_source_and_header():
+    """Every translation unit in csrc/ is in the Makefile's SRCS and every
+    header in its HDRS (text only): a file missing from SRCS is not in the
+    library, one missing from HDRS does not trigger a rebuild, and
+    scripts/build_exp.sh takes its source list from the same place."""
+    csrc = os.path.join(ROOT, "deep-sfm-revisited_amd", "csrc")
+    mk = open(os.path.join(csrc, "Makefile")).read().replace("\\\n", " ")
+    srcs = re.search(r"^SRCS\s*=(.*)$", mk, re.M).group(1).split()
+    hdrs = re.search(r"^HDRS\s*=(.*)$", mk, re.M).group(1).split()
+    files = sorted(os.listdir(csrc))
+    assert sorted(srcs) == [f for f in files if f.endswith((".hip", ".cpp"))]
+    assert sorted(h for h in hdrs if "/" not in h) == [f for f in files if f.endswith(".h")]
+    assert "print-srcs" in open(os.path.join(ROOT, "scripts", "build_exp.sh")).read()
+
+
 def test_reference_built_code_stays_in_the_build_container():
     """oracle/_ref (the reference's own sources compiled here, for golden
     generation only) never travels to the GPU box: .gpurunignore excludes it,

@@ -3,11 +3,11 @@ configs[4], C5: LO-RANSAC 8192 hypotheses + local E refinement, fp32 vs fp16
 inlier-set parity sweep).
 
 * 32 / 16 evaluate ComputeError<float> / <half> with E held in T
-  (ransac5.hip:inlier_lowp): bit-exact against the oracle's restatement
+  (score_valu.h:inlier_lowp): bit-exact against the oracle's restatement
   (ransac5_oracle.cpp:is_inlier_lp), itself checked against numpy
   float16/float32 arithmetic on the CPU.
 * 33 / 17 are the literal template form (double Ematrix, double products,
-  sums rounded to T; ransac5.hip:inlier_lowp_tpl vs is_inlier_lp_tpl).
+  sums rounded to T; score_valu.h:inlier_lowp_tpl vs is_inlier_lp_tpl).
 * C5 at full size: one KITTI pair (N = 435,032), H = 8192, each precision's
   winner refined by the GPU IRLS (optimise); the agreement table of
   DESIGN.md §C5 is asserted here against its documented bounds."""

@@ -141,6 +141,7 @@ const TuneKey kTuneKeys[] = {
 // and these select which call writes an output, not how a kernel runs.
 const TuneKey kSwitchKeys[] = {
     {"score_ref_rider", &sfm::Tuning::score_ref_rider, v_01},
+    {"sweep_fused_cl", &sfm::Tuning::sweep_fused_cl, v_01},
 };
 const TuneKey* find_key(const char* key) {
   for (const TuneKey& k : kTuneKeys)

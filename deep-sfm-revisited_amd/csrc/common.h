@@ -52,6 +52,9 @@ struct Tuning {
   int conv_rolling = 1;          // 1: cin-32 conv layers roll along the planes (k_conv3r); 0: k_conv3
   int score_ref_rider = 1;       // the cost volume's reference half written by the one-sided scorer's first
                                  // launch (sfm_score_ref_job; score_mf2.h); 0: the sweep writes both halves
+  int sweep_fused_cl = 1;        // read by the Python depth stage only (sfm_amd.regularize.fused_channels_last): 1: the
+                                 // sweep writes the regulariser's channels-last input itself (sfm_plane_sweep_cl);
+                                 // 0: planar volume, then sfm_to_channels_last_*
 };
 Tuning& tuning();
 

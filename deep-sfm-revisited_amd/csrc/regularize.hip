@@ -22,6 +22,7 @@
 // fp32 and stores bf16 four channels at a time (or, for the last layer, the
 // single output channel as fp32 [B][D][H][W], the layout the depth head reads).
 #include "common.h"
+#include "act_cvt.h"
 #include <type_traits>
 
 namespace sfm {
@@ -45,12 +46,7 @@ static_assert(kConvThreads == 4 * kTileX && kHaloY * 8 <= kConvThreads, "staging
 
 __device__ __forceinline__ int swz(int chunk, int row) { return chunk ^ ((row >> 2) & 3); }
 
-__device__ __forceinline__ float bf2f(unsigned short b) { return __uint_as_float((unsigned int)b << 16); }
-
-__device__ __forceinline__ unsigned short f2bf(float f) {  // RNE (v_cvt_pk_bf16_f32)
-  const __bf16 v = (__bf16)f;
-  return __builtin_bit_cast(unsigned short, v);
-}
+// (bf2f / f2bf and the per-type conversions ActCvt<F16>: act_cvt.h, shared with the sweep)
 
 // 16-bit activation type of the low-precision stack: bf16 (8-bit mantissa,
 // the fast opt-in) or f16 (11-bit mantissa: what the reference's Conv3d
@@ -58,20 +54,14 @@ __device__ __forceinline__ unsigned short f2bf(float f) {  // RNE (v_cvt_pk_bf16
 // cfgs/kitti.yml:10).  Same tiling; the MFMA and the conversions differ.
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 template <bool F16> struct Act;
-template <> struct Act<false> {
+template <> struct Act<false> : ActCvt<false> {
   using v8 = bf16x8;
-  static __device__ __forceinline__ float to_f(unsigned short b) { return bf2f(b); }
-  static __device__ __forceinline__ unsigned short from_f(float f) { return f2bf(f); }
   static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
   }
 };
-template <> struct Act<true> {
+template <> struct Act<true> : ActCvt<true> {
   using v8 = f16x8;
-  static __device__ __forceinline__ float to_f(unsigned short b) { return (float)__builtin_bit_cast(_Float16, b); }
-  static __device__ __forceinline__ unsigned short from_f(float f) {   // RNE (v_cvt_f16_f32)
-    return __builtin_bit_cast(unsigned short, (_Float16)f);
-  }
   static __device__ __forceinline__ f32x16 mfma(v8 a, v8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
   }

@@ -3,7 +3,8 @@
 Host-side mirror of the reference's operator interfaces over the C ABI of
 libsfm_hip.so (include/sfm_hip.h):
   ransac   batched RANSAC five-point (essential_matrix extension), flow -> points
-  sweep    plane-sweep cost volume, inverse_warp, PSNet sweep section
+  sweep    plane-sweep cost volume (planar, or channels-last for the regulariser), inverse_warp,
+           PSNet sweep section
   regularize  PSNet 3-D cost regularisation (dres0..classify) on the matrix cores
   synth    seeded synthetic KITTI-shaped inputs
   dist     one-process-per-GPU pair sharding and RCCL metric gather

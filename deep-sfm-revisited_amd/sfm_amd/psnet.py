@@ -7,7 +7,8 @@ and runs its forward with the hot path on libsfm_hip:
 
   feature_extraction  2-D CNN at 1/4 resolution, 32 channels         torch (MIOpen)
                       (PSMNet SPP layout, models/submodule.py:108-184)
-  plane sweep         cost [B, 64, L, h, w] (PSNet.py:130-158)        sfm_plane_sweep (HIP)
+  plane sweep         cost [B, 64, L, h, w] (PSNet.py:130-158)        sfm_plane_sweep (HIP); by default written
+                      channels-last for the next stage                 sfm_plane_sweep_cl (HIP)
   dres0..4, classify  3-D cost regularisation (PSNet.py:79-102, 159-165)  sfm_conv3_* (HIP MFMA)
   convs               per-plane context CNN (PSNET_CONTEXT, 175-192)   torch (MIOpen)
   head                trilinear up, softmax, disparity regression     sfm_depth_head (HIP)
@@ -24,7 +25,7 @@ import torch.nn.functional as F
 
 from .config import cfg as _default_cfg
 from .depth import depth_head
-from .regularize import CostRegularization
+from .regularize import CostRegularization, fused_channels_last, sweep_regularize_fused
 from .sweep import plane_sweep_cost, quarter_intrinsics
 
 
@@ -160,10 +161,16 @@ class PSNet(CostRegularization):
         costs = None
         for j, target in enumerate(targets):
             tgt_fea = self.feature_extraction(target).float()
-            cost = plane_sweep_cost(ref_fea.contiguous(), tgt_fea.contiguous(), pose[:, j].float().contiguous(),
-                                    K4, Ki4, self.nlabel, self.mindepth, dtype=self.cost_dtype,
-                                    predict_by_depth=pbd)
-            c0 = self.regularize(cost)
+            if fused_channels_last(self.cost_dtype, self.conv_precision):
+                # the sweep writes the stack's channels-last input itself: the same bits, no planar volume
+                c0 = sweep_regularize_fused(self, ref_fea.contiguous(), tgt_fea.contiguous(),
+                                            pose[:, j].float().contiguous(), K4, Ki4, self.nlabel, self.mindepth,
+                                            self.conv_precision, pbd)
+            else:
+                cost = plane_sweep_cost(ref_fea.contiguous(), tgt_fea.contiguous(),
+                                        pose[:, j].float().contiguous(), K4, Ki4, self.nlabel, self.mindepth,
+                                        dtype=self.cost_dtype, predict_by_depth=pbd)
+                c0 = self.regularize(cost)
             costs = c0 if costs is None else costs + c0
         costs = costs / len(targets)                                   # [B, 1, L, h, w]
         B, _, L, h, w = costs.shape

@@ -28,7 +28,7 @@ import torch.nn as nn
 
 from . import _lib
 from .depth import depth_head
-from .sweep import plane_sweep_cost, quarter_intrinsics
+from .sweep import plane_sweep_cost, plane_sweep_cost_channels_last, quarter_intrinsics
 
 
 _ACT_DTYPE = {"fp32": torch.float32, "fp32x3": torch.float32, "fp16": torch.float16, "bf16": torch.bfloat16}
@@ -52,20 +52,22 @@ def convbn_3d(in_planes, out_planes, kernel_size=3, stride=1, pad=1):
 
 
 _LP_NAME = {torch.bfloat16: "bf16", torch.float16: "f16"}
+_CL_NAME = dict(_LP_NAME)
+_CL_NAME[torch.float32] = "f32"
 
 
 def to_channels_last(cost, dtype=torch.bfloat16):
     """[B, C, L, h, w] fp32/bf16 (device) -> [B, L, h, w, C] ``dtype`` (bf16 or
-    fp16, round to nearest even)."""
+    fp16, round to nearest even; or float32, sfm_to_channels_last_f32)."""
     if not (isinstance(cost, torch.Tensor) and cost.is_cuda) or cost.dtype not in (torch.float32, torch.bfloat16):
         raise RuntimeError("to_channels_last needs a float32 / bfloat16 device tensor")
-    if dtype not in _LP_NAME:
-        raise RuntimeError("to_channels_last writes bfloat16 or float16")
+    if dtype not in _CL_NAME:
+        raise RuntimeError("to_channels_last writes bfloat16, float16 or float32")
     cost = cost.contiguous()
     B, C = cost.shape[:2]
     P = cost[0, 0].numel()
     out = torch.empty((B,) + tuple(cost.shape[2:]) + (C,), dtype=dtype, device=cost.device)
-    fn = "sfm_to_channels_last_" + _LP_NAME[dtype]
+    fn = "sfm_to_channels_last_" + _CL_NAME[dtype]
     with torch.cuda.device(cost.device):
         _lib.check(getattr(_lib.load(), fn)(_lib.ptr(cost), 0 if cost.dtype == torch.float32 else 1,
                                             B, C, P, _lib.ptr(out), _lib.stream_ptr(cost.device)), fn)
@@ -204,11 +206,29 @@ class CostRegularization(nn.Module):
         packed = self.pack(cost.device, precision)
         if C != packed[0]["cin"]:
             raise RuntimeError(f"cost has {C} channels, the first layer expects {packed[0]['cin']}")
-        lib = _lib.load()
-        dev = cost.device
+        return self.forward_channels_last(to_channels_last(cost, _ACT_DTYPE[precision]), precision=precision)
+
+    def forward_channels_last(self, x, precision="fp32x3"):
+        """``forward`` on the channels-last volume: x [B, L, h, w, Cin],
+        contiguous, in the precision's activation dtype (float32 for "fp32" /
+        "fp32x3", float16 for "fp16", bfloat16 for "bf16") -- what
+        ``to_channels_last`` or ``plane_sweep_cost_channels_last`` writes --
+        -> [B, 1, L, h, w] fp32."""
+        if precision not in _ACT_DTYPE:
+            raise ValueError(f"unknown conv precision {precision!r}")
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            raise RuntimeError("CostRegularization.forward_channels_last needs a device tensor (HIP path, no CPU "
+                               "fallback)")
         adt = _ACT_DTYPE[precision]
+        if x.dtype != adt or x.dim() != 5 or not x.is_contiguous():
+            raise RuntimeError(f"x must be a contiguous [B, L, h, w, C] {adt} tensor for precision {precision!r}")
+        B, L, h, w, C = x.shape
+        packed = self.pack(x.device, precision)
+        if C != packed[0]["cin"]:
+            raise RuntimeError(f"x has {C} channels, the first layer expects {packed[0]['cin']}")
+        lib = _lib.load()
+        dev = x.device
         suffix = {"fp32": "f32", "fp32x3": "f32", "fp16": "f16", "bf16": "bf16"}[precision]
-        to_cl = getattr(lib, "sfm_to_channels_last_" + suffix)
         if precision == "fp32x3":
             # the split-f16 kernel takes the weights' power-of-two exponent after them
             x3 = lib.sfm_conv3_f32x3
@@ -218,9 +238,6 @@ class CostRegularization(nn.Module):
             fn_name = "sfm_conv3_" + suffix
         with torch.cuda.device(dev):
             stream = _lib.stream_ptr(dev)
-            x = torch.empty((B, L, h, w, C), dtype=adt, device=dev)
-            _lib.check(to_cl(_lib.ptr(cost), 0 if cost.dtype == torch.float32 else 1, B, C, L * h * w, _lib.ptr(x),
-                             stream), "sfm_to_channels_last")
             bufs = [torch.empty((B, L, h, w, 32), dtype=adt, device=dev) for _ in range(3)]
             out = torch.empty((B, 1, L, h, w), dtype=torch.float32, device=dev)
             # fp32x3: one range flag per layer -- a layer whose input leaves the
@@ -249,17 +266,51 @@ class CostRegularization(nn.Module):
         return out
 
 
+def fused_channels_last(cost_dtype, precision):
+    """Whether the depth stage takes the fused route for this sweep storage
+    dtype and conv precision: the sweep writes the regulariser's channels-last
+    input itself (``plane_sweep_cost_channels_last``) instead of a planar
+    float32 volume that ``to_channels_last`` re-reads.  Same bits either way.
+    Only a float32 volume has a fused equivalent (a bf16 volume rounds twice),
+    and the library switch ``sweep_fused_cl`` (default 1) turns the route off."""
+    return cost_dtype == torch.float32 and precision in _ACT_DTYPE and _lib.tune_get("sweep_fused_cl") == 1
+
+
+def sweep_regularize_fused(regularizer, ref_fea, tgt_fea, pose, K4, Ki4, nlabel, min_depth, precision,
+                           predict_by_depth=False):
+    """Sweep + regularisation on the fused route: [B, 1, L, h, w] fp32, the
+    bits of ``regularizer(plane_sweep_cost(...), precision=precision)``."""
+    if precision not in _ACT_DTYPE:
+        raise ValueError(f"unknown conv precision {precision!r}")
+    x = plane_sweep_cost_channels_last(ref_fea, tgt_fea, pose, K4, Ki4, nlabel, min_depth,
+                                       dtype=_ACT_DTYPE[precision], predict_by_depth=predict_by_depth)
+    return CostRegularization.forward_channels_last(regularizer, x, precision=precision)
+
+
 def psnet_depth(ref_fea, tgt_fea, pose, intrinsics, intrinsics_inv, regularizer, nlabel, min_depth=1.0,
                 out_hw=None, predict_by_depth=False, cost_dtype=torch.float32, precision=None):
     """PSNet's single-target depth path at feature resolution, PSNet.py:130-216
     without the context network (cfg.PSNET_CONTEXT off): plane sweep ->
     dres/classify -> trilinear upsample, softmax, disparity regression.
     ``pose`` [B,3,4] already rescaled; full-resolution intrinsics.
-    Returns depth [B, 1, H, W] fp32."""
+    Returns depth [B, 1, H, W] fp32.  A stock ``CostRegularization`` with a
+    float32 volume takes the fused sweep (``fused_channels_last``); a subclass
+    that overrides ``forward``, a module with forward hooks and any other
+    callable get ``regularizer(cost)`` on the planar volume as before."""
     K4, Ki4 = quarter_intrinsics(intrinsics, intrinsics_inv)
-    cost = plane_sweep_cost(ref_fea, tgt_fea, pose, K4, Ki4, nlabel, min_depth, dtype=cost_dtype,
-                            predict_by_depth=predict_by_depth)
-    costs = regularizer(cost) if precision is None else regularizer(cost, precision=precision)
+    # the fused route calls forward_channels_last directly, so it is taken only where regularizer(cost) would
+    # run the stock forward and nothing else: no forward override and no forward (pre-)hooks on the module
+    fused = isinstance(regularizer, CostRegularization) and \
+        type(regularizer).forward is CostRegularization.forward and \
+        not regularizer._forward_hooks and not regularizer._forward_pre_hooks and \
+        fused_channels_last(cost_dtype, "fp32x3" if precision is None else precision)
+    if fused:
+        costs = sweep_regularize_fused(regularizer, ref_fea, tgt_fea, pose, K4, Ki4, nlabel, min_depth,
+                                       "fp32x3" if precision is None else precision, predict_by_depth)
+    else:
+        cost = plane_sweep_cost(ref_fea, tgt_fea, pose, K4, Ki4, nlabel, min_depth, dtype=cost_dtype,
+                                predict_by_depth=predict_by_depth)
+        costs = regularizer(cost) if precision is None else regularizer(cost, precision=precision)
     B = costs.shape[0]
     h, w = costs.shape[-2:]
     H, W = out_hw if out_hw is not None else (4 * h, 4 * w)

@@ -84,6 +84,46 @@ def plane_sweep_cost(ref_fea, tgt_fea, pose, intrinsics4, intrinsics_inv4, nlabe
     return out
 
 
+_CL_CODE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+
+
+def plane_sweep_cost_channels_last(ref_fea, tgt_fea, pose, intrinsics4, intrinsics_inv4, nlabel, min_depth=1.0,
+                                   dtype=torch.float16, out=None, workspace=None, predict_by_depth=False):
+    """The cost volume of ``plane_sweep_cost`` written channels-last,
+    [B, L, h, w, 2C] in ``dtype`` (float32, float16 or bfloat16): the tensor
+    the regularisation stack reads (PSNet.py:159), bit-identical to
+    ``to_channels_last(plane_sweep_cost(..., dtype=float32), dtype)`` without
+    the planar volume in between (sfm_plane_sweep_cl).  Arguments as
+    ``plane_sweep_cost``."""
+    _refuse_grad(ref_fea=ref_fea, tgt_fea=tgt_fea, pose=pose, intrinsics4=intrinsics4,
+                 intrinsics_inv4=intrinsics_inv4)
+    tgt = _dev_f32(tgt_fea, "tgt_fea")
+    B, C, h, w = tgt.shape
+    ref = _dev_f32(ref_fea, "ref_fea")
+    if tuple(ref.shape) != (B, C, h, w):
+        raise RuntimeError(f"ref_fea shape {tuple(ref.shape)} != tgt_fea shape {(B, C, h, w)}")
+    pose = _dev_f32(pose.reshape(B, 3, 4), "pose")
+    K4 = _dev_f32(intrinsics4.reshape(B, 3, 3), "intrinsics")
+    Ki4 = _dev_f32(intrinsics_inv4.reshape(B, 3, 3), "intrinsics_inv")
+    if dtype not in _CL_CODE:
+        raise RuntimeError("channels-last cost dtype must be float32, float16 or bfloat16")
+    shape = (B, int(nlabel), h, w, 2 * C)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=tgt.device)
+    elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != tgt.device:
+        raise RuntimeError(f"out must be a contiguous {dtype} tensor of shape {shape} on {tgt.device}")
+    L = _lib.load()
+    if workspace is None:
+        workspace = workspace_for(B, C, h, w, tgt.device)
+    with torch.cuda.device(tgt.device):
+        rc = L.sfm_plane_sweep_cl(_lib.ptr(ref), _lib.ptr(tgt), B, C, h, w, _lib.ptr(pose), _lib.ptr(K4),
+                                  _lib.ptr(Ki4), int(nlabel), float(min_depth), 1 if predict_by_depth else 0,
+                                  _CL_CODE[dtype], _lib.ptr(out), _lib.ptr(workspace), workspace.numel(),
+                                  _lib.stream_ptr(tgt.device))
+        _lib.check(rc, "sfm_plane_sweep_cl")
+    return out
+
+
 def ref_planes_workspace_for(B, C, h, w, device):
     n = _lib.load().sfm_plane_sweep_ref_planes_workspace_bytes(B, C, h, w)
     return torch.empty(n, dtype=torch.uint8, device=device)

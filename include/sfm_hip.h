@@ -237,6 +237,31 @@ int sfm_plane_sweep_ex(const float* ref, const float* tgt, int batch, int channe
                        int nlabel, float min_depth, int depth_mode, int out_dtype, void* cost,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same cost volume (models/PSNet.py:144-157) written channels-last, in the
+ * layout and activation type its consumer, the regularisation stack
+ * (PSNet.py:159; sfm_conv3_*), reads: what sfm_plane_sweep_ex into a float32
+ * volume followed by sfm_to_channels_last_{f32,bf16,f16} produce, bit for
+ * bit, without the planar [batch, 2C, nlabel, h, w] volume in between.
+ *   out[b, i, y, x, c]     = ref[b, c, y, x]                     (c < C)
+ *   out[b, i, y, x, C + c] = inverse_warp(tgt, d_i)[b, c, y, x]
+ * Arguments as sfm_plane_sweep_ex (ref is required; predict_by_depth is its
+ * depth_mode), and
+ *   out_dtype 0: float32, 1: bfloat16, 2: float16 (both round to nearest even,
+ *             the conversion of sfm_to_channels_last_*)
+ *   out       [dev] batch x nlabel x h x w x 2C, 16-byte aligned
+ *   workspace sfm_plane_sweep_workspace_bytes(batch, channels, h, w).
+ * nlabel * h * w < 2^31.  channels a multiple of 4 (float32) or 8 (16-bit)
+ * with every pair's tensors below 4 GiB take the wide-store kernel, any other
+ * shape an element-wise one: the same values.  The switch "sweep_fused_cl"
+ * (sfm_tune_set; 0, 1; default 1; not enumerated by sfm_tune_key) is not read
+ * here: it tells a caller that owns both routes (sfm_amd.regularize) which one
+ * to take. */
+int sfm_plane_sweep_cl(const float* ref, const float* tgt, int batch, int channels, int h, int w,
+                       const float* pose, const float* K4, const float* K4inv,
+                       int nlabel, float min_depth, int predict_by_depth,
+                       int out_dtype /* 0 fp32, 1 bf16, 2 f16 */,
+                       void* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The sweep section of PSNet.forward from the pose stage's outputs, in one
  * call (models/PSNet.py:130-157): the reference's tensor preparation runs in a
  * one-thread-per-pair kernel instead of ~10 ATen launches, bit for bit:

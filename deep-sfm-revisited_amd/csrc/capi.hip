@@ -142,6 +142,7 @@ const TuneKey kTuneKeys[] = {
 const TuneKey kSwitchKeys[] = {
     {"score_ref_rider", &sfm::Tuning::score_ref_rider, v_01},
     {"sweep_fused_cl", &sfm::Tuning::sweep_fused_cl, v_01},
+    {"sweep_f16_feat", &sfm::Tuning::sweep_f16_feat, v_01},
 };
 const TuneKey* find_key(const char* key) {
   for (const TuneKey& k : kTuneKeys)

@@ -55,6 +55,9 @@ struct Tuning {
   int sweep_fused_cl = 1;        // read by the Python depth stage only (sfm_amd.regularize.fused_channels_last): 1: the
                                  // sweep writes the regulariser's channels-last input itself (sfm_plane_sweep_cl);
                                  // 0: planar volume, then sfm_to_channels_last_*
+  int sweep_f16_feat = 1;        // read by the Python depth stage only (sfm_amd.regularize.sweep_regularize_fused,
+                                 // sfm_amd.psnet): 1: float16 features go to the fused sweep as they come
+                                 // (sfm_plane_sweep_cl_f16); 0: widened to float32 first (sfm_plane_sweep_cl)
 };
 Tuning& tuning();
 

@@ -42,6 +42,7 @@ constexpr int kSwPix = 4;
 constexpr int kSwWin = kSwThreads * kSwPix;
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float plane_depth(float dmax, float dstep, int l) {
   // PSNet.py:150-153: depth planes (i+1)*MIN_DEPTH, or disp2depth / (i+1)
@@ -85,12 +86,34 @@ __device__ __forceinline__ void psnet_prep_pair(const PsnetPrep& q, int B, int b
   }
 }
 
-// tgt [B][C][hw] -> tq [B][C4][hw] float4 (channels >= C are zero).  With
-// `projs`, threads 0..B-1 also write each pair's Proj (K.pose rows and K^-1,
-// load_proj's float32 expression order), so the sweep's waves read it with
-// scalar loads instead of each recomputing the uniform 3x3.3x4 product on the
-// VALU (~80 instructions per wave item); threads 0..L-1 the plane depths
-// (two IEEE divisions per wave item otherwise).
+// The uniform tables the relayout kernels write beside their copy, from the
+// first record row of pair 0.  With `projs`, threads 0..B-1 write each pair's
+// Proj (K.pose rows and K^-1, load_proj's float32 expression order), so the
+// sweep's waves read it with scalar loads instead of each recomputing the
+// uniform 3x3.3x4 product on the VALU (~80 instructions per wave item);
+// threads 0..L-1 the plane depths (two IEEE divisions per wave item otherwise).
+__device__ __forceinline__ void write_sweep_tables(int i, int B, const float* __restrict__ pose,
+                                                   const float* __restrict__ K4, const float* __restrict__ K4inv,
+                                                   Proj* __restrict__ projs, int L, float dmax, float dstep,
+                                                   float* __restrict__ depths, const PsnetPrep& prep) {
+  if (projs && i < B) {
+    // sfm_plane_sweep_psnet: the pair's PSNet preparation first (the sweep's
+    // other paths read it from the workspace), then its Proj from those values
+    Proj pr;
+    if (prep.out) {
+      float P[12], Kq[9], Kqi[9];
+      psnet_prep_pair(prep, B, i, P, Kq, Kqi);
+      load_proj(P, Kq, Kqi, 0, pr);
+    } else {
+      load_proj(pose, K4, K4inv, i, pr);
+    }
+    projs[i] = pr;
+  }
+  if (depths && i < L) depths[i] = plane_depth(dmax, dstep, i);
+}
+
+// tgt [B][C][hw] -> tq [B][C4][hw] float4 (channels >= C are zero), and the
+// sweep's tables (write_sweep_tables).
 __global__ void k_tgt_quads(const float* __restrict__ tgt, int B, int C, int C4, int hw, f32x4* __restrict__ tq,
                             const float* __restrict__ pose, const float* __restrict__ K4,
                             const float* __restrict__ K4inv, Proj* __restrict__ projs, int L, float dmax,
@@ -99,22 +122,7 @@ __global__ void k_tgt_quads(const float* __restrict__ tgt, int B, int C, int C4,
   // per-pair and per-plane tables from the first quad row of pair 0
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   const int q = (int)blockIdx.y, b = (int)blockIdx.z;
-  if (q == 0 && b == 0) {
-    if (projs && i < B) {
-      // sfm_plane_sweep_psnet: the pair's PSNet preparation first (the sweep's
-      // other paths read it from the workspace), then its Proj from those values
-      Proj pr;
-      if (prep.out) {
-        float P[12], Kq[9], Kqi[9];
-        psnet_prep_pair(prep, B, i, P, Kq, Kqi);
-        load_proj(P, Kq, Kqi, 0, pr);
-      } else {
-        load_proj(pose, K4, K4inv, i, pr);
-      }
-      projs[i] = pr;
-    }
-    if (depths && i < L) depths[i] = plane_depth(dmax, dstep, i);
-  }
+  if (q == 0 && b == 0) write_sweep_tables(i, B, pose, K4, K4inv, projs, L, dmax, dstep, depths, prep);
   if (i >= hw) return;
   f32x4 v;
 #pragma unroll
@@ -123,6 +131,29 @@ __global__ void k_tgt_quads(const float* __restrict__ tgt, int B, int C, int C4,
     v[k] = c < C ? tgt[((size_t)b * C + c) * hw + i] : 0.0f;
   }
   tq[((size_t)b * C4 + q) * hw + i] = v;
+}
+
+// The same for float16 features, which stay float16: tgt [B][C][hw] IEEE half
+// (raw 16-bit patterns) -> to [B][C8][hw] octets of eight halves, 16 bytes like
+// a quad, so one gather brings eight channels of a tap (channels >= C are
+// zero).  The tables are k_tgt_quads' (the sweep's geometry is the same bits).
+__global__ void k_tgt_octets(const unsigned short* __restrict__ tgt, int B, int C, int C8, int hw,
+                             u32x4* __restrict__ to, const float* __restrict__ pose, const float* __restrict__ K4,
+                             const float* __restrict__ K4inv, Proj* __restrict__ projs, int L, float dmax,
+                             float dstep, float* __restrict__ depths) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  const int o = (int)blockIdx.y, b = (int)blockIdx.z;
+  if (o == 0 && b == 0) write_sweep_tables(i, B, pose, K4, K4inv, projs, L, dmax, dstep, depths, PsnetPrep{});
+  if (i >= hw) return;
+  u32x4 v;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int c = 8 * o + 2 * k;
+    const unsigned lo = c < C ? tgt[((size_t)b * C + c) * hw + i] : 0u;
+    const unsigned hi = c + 1 < C ? tgt[((size_t)b * C + c + 1) * hw + i] : 0u;
+    v[k] = lo | (hi << 16);
+  }
+  to[((size_t)b * C8 + o) * hw + i] = v;
 }
 
 static dim3 quads_grid(int B, int C4, int hw, int extra) {
@@ -608,7 +639,6 @@ template <typename OutT> struct TileLanes;
 template <> struct TileLanes<float> { static constexpr int AM = 63; };
 template <> struct TileLanes<unsigned short> { static constexpr int AM = 127; };
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 // a wave's LDS stage handed between its lanes: the compiler keeps every
 // memory access on its side (the "memory" clobber; wavefront-scope fences do
@@ -1761,6 +1791,15 @@ static size_t ref_planes_ws_bytes(int B, int C, int h, int w) {
 // below 2^32, h * w < 2^24, a record stage of at most 64 KB per wave.  Every
 // other shape takes k_sweep_cl_any (one thread per record, element stores,
 // 64-bit indices).
+//
+// Float16 features (F16 = true; sfm_plane_sweep_cl_f16): `ref` is the planar
+// half tensor and the target comes as k_tgt_octets' records, so the warped
+// half gathers 4 octets per 8 channels where the float32 form gathers 8 quads.
+// Every half is widened to float32 (exact, subnormals included) before the
+// unchanged tap sum and the unchanged rounding, so the volume is the one the
+// float32 form writes for the widened features, bit for bit.  With a float32
+// output an octet fills two record chunks.  Fast path: C % 8 == 0 for every
+// output type, and the limits above.
 // ---------------------------------------------------------------------------
 #ifndef SFM_SWEEP_CL_POLICY
 #define SFM_SWEEP_CL_POLICY 16   // cache policy of the record stores (0 plain, 3 sc0 nt, 16 sc1, 17 sc0 sc1, 18 nt sc1)
@@ -1782,8 +1821,19 @@ template <> struct ClOut<BF16Out> {
   static __device__ __forceinline__ unsigned short cvt(float f) { return ActCvt<false>::from_f(f); }
 };
 
+// the features' storage: float32 and channel quads, or IEEE half (raw 16-bit patterns) and channel octets
+template <bool F16> struct ClFeat;
+template <> struct ClFeat<false> {
+  using elem = float;
+  using rec = f32x4;
+};
+template <> struct ClFeat<true> {
+  using elem = unsigned short;
+  using rec = u32x4;
+};
+
 struct ClGeom {
-  int B, C, C4, h, w, hw, L;
+  int B, C, C4, h, w, hw, L;   // C4: 16-byte target records per pixel (quads, or octets of float16 features)
   int R;                 // 16-byte chunks per record
   int slab;              // pixel-planes (records) per pair: L * hw < 2^31
   unsigned pair_bytes;   // one pair's records in bytes (fast path)
@@ -1818,11 +1868,13 @@ __device__ __forceinline__ u32x4 cl_pack(const float* v) {
 
 constexpr int kClThreads = 256;
 
-template <typename OutT, int POL>
-__global__ __launch_bounds__(kClThreads) void k_sweep_cl(const float* __restrict__ ref, const f32x4* __restrict__ tq,
+template <typename OutT, int POL, bool F16 = false>
+__global__ __launch_bounds__(kClThreads) void k_sweep_cl(const typename ClFeat<F16>::elem* __restrict__ ref,
+                                                         const typename ClFeat<F16>::rec* __restrict__ tq,
                                                          const Proj* __restrict__ projs, ClGeom g,
                                                          typename ClOut<OutT>::elem* __restrict__ out) {
   using E = typename ClOut<OutT>::elem;
+  constexpr unsigned FB = (unsigned)sizeof(typename ClFeat<F16>::elem);   // bytes per feature element
   constexpr int EPC = 16 / (int)sizeof(E);      // channels per chunk
   constexpr int QPC = EPC / 4;                  // channel quads per chunk
   extern __shared__ __attribute__((aligned(16))) u32x4 s_stage[];   // [waves][64][R + 1]
@@ -1850,7 +1902,7 @@ __global__ __launch_bounds__(kClThreads) void k_sweep_cl(const float* __restrict
   const bool in = sample_pos_nr(pr, ray, d, sk, ix, iy);
   TapsIn tp;
   if (in) make_taps_inside(ix, iy, g.h, g.w, tp);
-  const __amdgpu_buffer_rsrc_t rref = buf_rsrc(ref + (size_t)b * g.C * g.hw, (unsigned)g.C * g.hw * 4u);
+  const __amdgpu_buffer_rsrc_t rref = buf_rsrc(ref + (size_t)b * g.C * g.hw, (unsigned)g.C * g.hw * FB);
   const __amdgpu_buffer_rsrc_t rtq = buf_rsrc(tq + (size_t)b * g.C4 * g.hw, (unsigned)g.C4 * g.hw * 16u);
   const __amdgpu_buffer_rsrc_t rout = buf_rsrc(out + (size_t)b * g.slab * 2 * g.C, g.pair_bytes);
   const int R = g.R, RH = R >> 1;               // the reference half and the warped half: RH chunks each
@@ -1859,33 +1911,63 @@ __global__ __launch_bounds__(kClThreads) void k_sweep_cl(const float* __restrict
   for (int k = 0; k < RH; ++k) {
     float v[EPC];
 #pragma unroll
-    for (int e = 0; e < EPC; ++e)
-      v[e] = __uint_as_float(
-          __builtin_amdgcn_raw_buffer_load_b32(rref, (unsigned)p * 4u, (unsigned)(k * EPC + e) * g.hw * 4u, 0));
+    for (int e = 0; e < EPC; ++e) {
+      const unsigned so = (unsigned)(k * EPC + e) * g.hw * FB;
+      if constexpr (F16)   // through float32 and cl_pack's cvt, like the warped half: one function defines the rounding
+        v[e] = ActCvt<true>::to_f((unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rref, (unsigned)p * 2u, so, 0));
+      else
+        v[e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rref, (unsigned)p * 4u, so, 0));
+    }
     emit(k, v);
   }
-  for (int k = 0; k < RH; ++k) {
-    float v[EPC];
+  if constexpr (F16) {
+    constexpr int CPO = 8 / EPC;                // record chunks an octet fills: 1 (16-bit) or 2 (float32)
+    for (int o = 0; o < RH / CPO; ++o) {
+      float v[8];
 #pragma unroll
-    for (int e = 0; e < EPC; ++e) v[e] = 0.0f;  // an out-of-image sample: zero for every channel
-    if (in) {
+      for (int e = 0; e < 8; ++e) v[e] = 0.0f;    // an out-of-image sample: zero for every channel
+      if (in) {
+        const unsigned so = (unsigned)o * g.hw * 16u;
+        u32x4 t[4];
 #pragma unroll
-      for (int q = 0; q < QPC; ++q) {
-        const unsigned so = (unsigned)(k * QPC + q) * g.hw * 16u;
-        f32x4 t[4];
+        for (int n = 0; n < 4; ++n)
+          t[n] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rtq, tp.off[n] * 16u, so, 0));
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
-          t[e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rtq, tp.off[e] * 16u, so, 0));
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float a = tp.wt[0] * t[0][e];
-          a = __builtin_fmaf(tp.wt[1], t[1][e], a);
-          a = __builtin_fmaf(tp.wt[2], t[2][e], a);
-          v[4 * q + e] = cl_f32(__builtin_fmaf(tp.wt[3], t[3][e], a));
+        for (int e = 0; e < 8; ++e) {
+          auto tap = [&](int n) { return ActCvt<true>::to_f((unsigned short)(t[n][e >> 1] >> (16 * (e & 1)))); };
+          float a = tp.wt[0] * tap(0);
+          a = __builtin_fmaf(tp.wt[1], tap(1), a);
+          a = __builtin_fmaf(tp.wt[2], tap(2), a);
+          v[e] = cl_f32(__builtin_fmaf(tp.wt[3], tap(3), a));
         }
       }
+#pragma unroll
+      for (int c = 0; c < CPO; ++c) emit(RH + o * CPO + c, v + c * EPC);
     }
-    emit(RH + k, v);
+  } else {
+    for (int k = 0; k < RH; ++k) {
+      float v[EPC];
+#pragma unroll
+      for (int e = 0; e < EPC; ++e) v[e] = 0.0f;  // an out-of-image sample: zero for every channel
+      if (in) {
+#pragma unroll
+        for (int q = 0; q < QPC; ++q) {
+          const unsigned so = (unsigned)(k * QPC + q) * g.hw * 16u;
+          f32x4 t[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            t[e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rtq, tp.off[e] * 16u, so, 0));
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            float a = tp.wt[0] * t[0][e];
+            a = __builtin_fmaf(tp.wt[1], t[1][e], a);
+            a = __builtin_fmaf(tp.wt[2], t[2][e], a);
+            v[4 * q + e] = cl_f32(__builtin_fmaf(tp.wt[3], t[3][e], a));
+          }
+        }
+      }
+      emit(RH + k, v);
+    }
   }
   // the run in address order: chunk i of the run is chunk i % R of record i / R
   sweep_wave_sync();
@@ -1899,11 +1981,18 @@ __global__ __launch_bounds__(kClThreads) void k_sweep_cl(const float* __restrict
 }
 
 // any shape: one thread per record, element by element
-template <typename OutT>
-__global__ __launch_bounds__(256) void k_sweep_cl_any(const float* __restrict__ ref, const f32x4* __restrict__ tq,
+template <typename OutT, bool F16 = false>
+__global__ __launch_bounds__(256) void k_sweep_cl_any(const typename ClFeat<F16>::elem* __restrict__ ref,
+                                                      const typename ClFeat<F16>::rec* __restrict__ tq,
                                                       const Proj* __restrict__ projs, ClGeom g,
                                                       typename ClOut<OutT>::elem* __restrict__ out) {
   using O = ClOut<OutT>;
+  using FE = typename ClFeat<F16>::elem;
+  constexpr int CPR = 16 / (int)sizeof(FE);     // channels per target record: a quad or an octet
+  auto widen = [](FE v) {
+    if constexpr (F16) return ActCvt<true>::to_f(v);
+    else return v;
+  };
   const int64_t total = (int64_t)g.B * g.slab;
   const SampleK sk = sample_consts(g.h, g.w);
   for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
@@ -1922,25 +2011,25 @@ __global__ __launch_bounds__(256) void k_sweep_cl_any(const float* __restrict__ 
     TapsIn tp;
     if (in) make_taps_inside(ix, iy, g.h, g.w, tp);
     typename O::elem* rec = out + (size_t)t * 2 * g.C;
-    for (int c = 0; c < g.C; ++c) rec[c] = O::cvt(ref[((size_t)b * g.C + c) * g.hw + p]);
+    for (int c = 0; c < g.C; ++c) rec[c] = O::cvt(widen(ref[((size_t)b * g.C + c) * g.hw + p]));
     for (int c = 0; c < g.C; ++c) {
       float a = 0.0f;
       if (in) {
-        // channel c of the quad layout: element c & 3 of tq[b][c >> 2][pixel]
-        const float* T = reinterpret_cast<const float*>(tq + ((size_t)b * g.C4 + (c >> 2)) * g.hw) + (c & 3);
-        a = tp.wt[0] * T[(size_t)tp.off[0] * 4];
-        a = __builtin_fmaf(tp.wt[1], T[(size_t)tp.off[1] * 4], a);
-        a = __builtin_fmaf(tp.wt[2], T[(size_t)tp.off[2] * 4], a);
-        a = cl_f32(__builtin_fmaf(tp.wt[3], T[(size_t)tp.off[3] * 4], a));
+        // channel c of the record layout: element c % CPR of tq[b][c / CPR][pixel]
+        const FE* T = reinterpret_cast<const FE*>(tq + ((size_t)b * g.C4 + c / CPR) * g.hw) + c % CPR;
+        a = tp.wt[0] * widen(T[(size_t)tp.off[0] * CPR]);
+        a = __builtin_fmaf(tp.wt[1], widen(T[(size_t)tp.off[1] * CPR]), a);
+        a = __builtin_fmaf(tp.wt[2], widen(T[(size_t)tp.off[2] * CPR]), a);
+        a = cl_f32(__builtin_fmaf(tp.wt[3], widen(T[(size_t)tp.off[3] * CPR]), a));
       }
       rec[g.C + c] = O::cvt(a);
     }
   }
 }
 
-template <typename OutT>
-static int launch_k_sweep_cl(const float* ref, const f32x4* tq, const Proj* projs, const ClGeom& g, bool fast,
-                             void* out, hipStream_t s) {
+template <typename OutT, bool F16>
+static int launch_k_sweep_cl(const typename ClFeat<F16>::elem* ref, const typename ClFeat<F16>::rec* tq,
+                             const Proj* projs, const ClGeom& g, bool fast, void* out, hipStream_t s) {
   using E = typename ClOut<OutT>::elem;
   if (fast) {
     // the stage: 64 padded records per wave; as many waves per block as fit 40 KB (four blocks per CU)
@@ -1948,15 +2037,73 @@ static int launch_k_sweep_cl(const float* ref, const f32x4* tq, const Proj* proj
     int waves = kClThreads / 64;
     while (waves > 1 && waves * wave_lds > 40 * 1024) waves >>= 1;
     const unsigned blocks = (unsigned)(((int64_t)g.slab + 64 * waves - 1) / (64 * waves));
-    hipLaunchKernelGGL((k_sweep_cl<OutT, SFM_SWEEP_CL_POLICY>), dim3(blocks, (unsigned)g.B),
+    hipLaunchKernelGGL((k_sweep_cl<OutT, SFM_SWEEP_CL_POLICY, F16>), dim3(blocks, (unsigned)g.B),
                        dim3(64 * waves), waves * wave_lds, s, ref, tq, projs, g, (E*)out);
   } else {
     const int64_t total = (int64_t)g.B * g.slab;
     const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, (int64_t)1 << 20);
-    hipLaunchKernelGGL(k_sweep_cl_any<OutT>, dim3(blocks), dim3(256), 0, s, ref, tq, projs, g, (E*)out);
+    hipLaunchKernelGGL((k_sweep_cl_any<OutT, F16>), dim3(blocks), dim3(256), 0, s, ref, tq, projs, g, (E*)out);
   }
   SFM_LAUNCHED();
   return SFM_OK;
+}
+
+// sfm_plane_sweep_cl (F16 = false) and sfm_plane_sweep_cl_f16: the same checks, workspace and geometry; the
+// float16 form relays the target as octets, which fit the quads' region (ceil(C/8) records against ceil(C/4))
+template <bool F16>
+static int plane_sweep_cl(const typename ClFeat<F16>::elem* ref, const typename ClFeat<F16>::elem* tgt, int batch,
+                          int channels, int h, int w, const float* pose, const float* K4, const float* K4inv,
+                          int nlabel, float min_depth, int predict_by_depth, int out_dtype, void* out,
+                          void* workspace, size_t workspace_bytes, hipStream_t s) {
+  SFM_REQUIRE(ref && tgt && pose && K4 && K4inv && out && workspace, "null pointer argument");
+  // (the relayout's grid: records in y, pairs in z; make_taps_inside multiplies 24-bit row offsets)
+  SFM_REQUIRE(batch >= 1 && batch <= 65535 && channels >= 1 && channels <= 4 * 65535 && h >= 2 && w >= 2 &&
+                  h < (1 << 23) && w < (1 << 23) && nlabel >= 1,
+              "invalid sweep shape");
+  SFM_REQUIRE(out_dtype >= 0 && out_dtype <= 2, "out_dtype must be 0 (float32), 1 (bfloat16) or 2 (float16)");
+  SFM_REQUIRE(predict_by_depth == 0 || predict_by_depth == 1,
+              "predict_by_depth must be 0 (inverse depth) or 1 (depth)");
+  SFM_REQUIRE(min_depth > 0.0f, "min_depth must be positive");
+  SFM_REQUIRE((int64_t)h * w < ((int64_t)1 << 30), "feature map too large");
+  SFM_REQUIRE((int64_t)nlabel * h * w < ((int64_t)1 << 31), "sweep too large: nlabel * h * w must be below 2^31");
+  SFM_REQUIRE((uintptr_t)out % 16 == 0, "out must be 16-byte aligned");
+  const int B = batch, C = channels, L = nlabel, hw = h * w;
+  const size_t need = sweep_ws_bytes(B, C, h, w);
+  if (workspace_bytes < need) {
+    set_error("plane sweep workspace too small: need " + std::to_string(need) + " bytes");
+    return SFM_ERR_WORKSPACE;
+  }
+  const int esz = out_dtype == 0 ? 4 : 2;
+  ClGeom g;
+  g.B = B; g.C = C; g.C4 = F16 ? (C + 7) / 8 : (C + 3) / 4; g.h = h; g.w = w; g.hw = hw; g.L = L;
+  g.slab = L * hw;
+  g.dmax = min_depth * (float)L;   // disp2depth = ones * MIN_DEPTH * nlabel (fp32)
+  g.dstep = predict_by_depth ? min_depth : 0.0f;
+  g.inv_w = 1.0f / (float)w;
+  g.mhw = make_magic((unsigned)hw);
+  const int64_t rec_bytes = (int64_t)2 * C * esz, pair_bytes = rec_bytes * g.slab;
+  // whole 16-byte chunks per record half; with float16 features whole octets as well
+  const bool fast = C % (F16 ? 8 : 16 / esz) == 0 && rec_bytes / 16 <= 63 && hw < (1 << 24) &&
+                    pair_bytes < ((int64_t)1 << 32) && (int64_t)g.C4 * hw * 16 < ((int64_t)1 << 32);
+  g.R = fast ? (int)(rec_bytes / 16) : 0;
+  g.mR = make_magic((unsigned)std::max(g.R, 1));
+  g.pair_bytes = fast ? (unsigned)pair_bytes : 0u;
+  auto* tq = (typename ClFeat<F16>::rec*)workspace;
+  Proj* projs = reinterpret_cast<Proj*>((char*)workspace + sweep_quads_bytes(B, C, h, w));
+  {
+    ProfScope ps(F16 ? "sweep_tgt_octets" : "sweep_tgt_quads", s);
+    if constexpr (F16)
+      hipLaunchKernelGGL(k_tgt_octets, quads_grid(B, g.C4, hw, B), dim3(256), 0, s, tgt, B, C, g.C4, hw, tq, pose, K4,
+                         K4inv, projs, L, g.dmax, g.dstep, (float*)nullptr);
+    else
+      hipLaunchKernelGGL(k_tgt_quads, quads_grid(B, g.C4, hw, B), dim3(256), 0, s, tgt, B, C, g.C4, hw, tq, pose, K4,
+                         K4inv, projs, L, g.dmax, g.dstep, (float*)nullptr, PsnetPrep{});
+  }
+  SFM_LAUNCHED();
+  ProfScope ps(F16 ? "plane_sweep_cl_f16" : "plane_sweep_cl", s);
+  if (out_dtype == 0) return launch_k_sweep_cl<float, F16>(ref, tq, projs, g, fast, out, s);
+  if (out_dtype == 1) return launch_k_sweep_cl<BF16Out, F16>(ref, tq, projs, g, fast, out, s);
+  return launch_k_sweep_cl<F16Out, F16>(ref, tq, projs, g, fast, out, s);
 }
 
 }  // namespace sfm
@@ -2018,51 +2165,16 @@ int sfm_plane_sweep_psnet(const float* ref, const float* tgt, int batch, int cha
 int sfm_plane_sweep_cl(const float* ref, const float* tgt, int batch, int channels, int h, int w, const float* pose,
                        const float* K4, const float* K4inv, int nlabel, float min_depth, int predict_by_depth,
                        int out_dtype, void* out, void* workspace, size_t workspace_bytes, void* stream) {
-  SFM_REQUIRE(ref && tgt && pose && K4 && K4inv && out && workspace, "null pointer argument");
-  // (k_tgt_quads' grid: quads in y, pairs in z; make_taps_inside multiplies 24-bit row offsets)
-  SFM_REQUIRE(batch >= 1 && batch <= 65535 && channels >= 1 && channels <= 4 * 65535 && h >= 2 && w >= 2 &&
-                  h < (1 << 23) && w < (1 << 23) && nlabel >= 1,
-              "invalid sweep shape");
-  SFM_REQUIRE(out_dtype >= 0 && out_dtype <= 2, "out_dtype must be 0 (float32), 1 (bfloat16) or 2 (float16)");
-  SFM_REQUIRE(predict_by_depth == 0 || predict_by_depth == 1,
-              "predict_by_depth must be 0 (inverse depth) or 1 (depth)");
-  SFM_REQUIRE(min_depth > 0.0f, "min_depth must be positive");
-  SFM_REQUIRE((int64_t)h * w < ((int64_t)1 << 30), "feature map too large");
-  SFM_REQUIRE((int64_t)nlabel * h * w < ((int64_t)1 << 31), "sweep too large: nlabel * h * w must be below 2^31");
-  SFM_REQUIRE((uintptr_t)out % 16 == 0, "out must be 16-byte aligned");
-  const int B = batch, C = channels, L = nlabel, hw = h * w;
-  const size_t need = sweep_ws_bytes(B, C, h, w);
-  if (workspace_bytes < need) {
-    set_error("plane sweep workspace too small: need " + std::to_string(need) + " bytes");
-    return SFM_ERR_WORKSPACE;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const int esz = out_dtype == 0 ? 4 : 2;
-  ClGeom g;
-  g.B = B; g.C = C; g.C4 = (C + 3) / 4; g.h = h; g.w = w; g.hw = hw; g.L = L;
-  g.slab = L * hw;
-  g.dmax = min_depth * (float)L;   // disp2depth = ones * MIN_DEPTH * nlabel (fp32)
-  g.dstep = predict_by_depth ? min_depth : 0.0f;
-  g.inv_w = 1.0f / (float)w;
-  g.mhw = make_magic((unsigned)hw);
-  const int64_t rec_bytes = (int64_t)2 * C * esz, pair_bytes = rec_bytes * g.slab;
-  const bool fast = C % (16 / esz) == 0 && rec_bytes / 16 <= 63 && hw < (1 << 24) &&
-                    pair_bytes < ((int64_t)1 << 32) && (int64_t)g.C4 * hw * 16 < ((int64_t)1 << 32);
-  g.R = fast ? (int)(rec_bytes / 16) : 0;
-  g.mR = make_magic((unsigned)std::max(g.R, 1));
-  g.pair_bytes = fast ? (unsigned)pair_bytes : 0u;
-  f32x4* tq = (f32x4*)workspace;
-  Proj* projs = reinterpret_cast<Proj*>((char*)workspace + sweep_quads_bytes(B, C, h, w));
-  {
-    ProfScope ps("sweep_tgt_quads", s);
-    hipLaunchKernelGGL(k_tgt_quads, quads_grid(B, g.C4, hw, B), dim3(256), 0, s, tgt, B, C, g.C4, hw, tq, pose, K4,
-                       K4inv, projs, L, g.dmax, g.dstep, (float*)nullptr, PsnetPrep{});
-  }
-  SFM_LAUNCHED();
-  ProfScope ps("plane_sweep_cl", s);
-  if (out_dtype == 0) return launch_k_sweep_cl<float>(ref, tq, projs, g, fast, out, s);
-  if (out_dtype == 1) return launch_k_sweep_cl<BF16Out>(ref, tq, projs, g, fast, out, s);
-  return launch_k_sweep_cl<F16Out>(ref, tq, projs, g, fast, out, s);
+  return plane_sweep_cl<false>(ref, tgt, batch, channels, h, w, pose, K4, K4inv, nlabel, min_depth, predict_by_depth,
+                               out_dtype, out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int sfm_plane_sweep_cl_f16(const void* ref, const void* tgt, int batch, int channels, int h, int w, const float* pose,
+                           const float* K4, const float* K4inv, int nlabel, float min_depth, int predict_by_depth,
+                           int out_dtype, void* out, void* workspace, size_t workspace_bytes, void* stream) {
+  return plane_sweep_cl<true>((const unsigned short*)ref, (const unsigned short*)tgt, batch, channels, h, w, pose, K4,
+                              K4inv, nlabel, min_depth, predict_by_depth, out_dtype, out, workspace, workspace_bytes,
+                              (hipStream_t)stream);
 }
 
 size_t sfm_plane_sweep_ref_planes_workspace_bytes(int batch, int channels, int h, int w) {

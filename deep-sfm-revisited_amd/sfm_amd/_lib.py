@@ -51,6 +51,9 @@ _SIGS = [
     ("sfm_plane_sweep_cl", ctypes.c_int,
      [_c_dp, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp, ctypes.c_int,
       ctypes.c_float, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, ctypes.c_size_t, _c_dp]),
+    ("sfm_plane_sweep_cl_f16", ctypes.c_int,
+     [_c_dp, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp, ctypes.c_int,
+      ctypes.c_float, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, ctypes.c_size_t, _c_dp]),
     ("sfm_plane_sweep_psnet", ctypes.c_int,
      [_c_dp, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, ctypes.c_int, _c_dp, _c_dp,
       ctypes.c_float, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, ctypes.c_size_t,

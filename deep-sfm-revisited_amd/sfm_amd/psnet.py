@@ -8,7 +8,8 @@ and runs its forward with the hot path on libsfm_hip:
   feature_extraction  2-D CNN at 1/4 resolution, 32 channels         torch (MIOpen)
                       (PSMNet SPP layout, models/submodule.py:108-184)
   plane sweep         cost [B, 64, L, h, w] (PSNet.py:130-158)        sfm_plane_sweep (HIP); by default written
-                      channels-last for the next stage                 sfm_plane_sweep_cl (HIP)
+                      channels-last for the next stage                 sfm_plane_sweep_cl (HIP); float16 features
+                      (cfg.MIXED_PREC) read as they come               sfm_plane_sweep_cl_f16 (HIP)
   dres0..4, classify  3-D cost regularisation (PSNet.py:79-102, 159-165)  sfm_conv3_* (HIP MFMA)
   convs               per-plane context CNN (PSNET_CONTEXT, 175-192)   torch (MIOpen)
   head                trilinear up, softmax, disparity regression     sfm_depth_head (HIP)
@@ -25,7 +26,7 @@ import torch.nn.functional as F
 
 from .config import cfg as _default_cfg
 from .depth import depth_head
-from .regularize import CostRegularization, fused_channels_last, sweep_regularize_fused
+from .regularize import CostRegularization, f16_features, fused_channels_last, sweep_regularize_fused
 from .sweep import plane_sweep_cost, quarter_intrinsics
 
 
@@ -157,17 +158,27 @@ class PSNet(CostRegularization):
         if c.get("RESCALE_DEPTH", False):
             pose[:, 0, :, -1:] = pose[:, 0, :, -1:] * c.NORM_TARGET      # in place, PSNet.py:135-136
         pbd = bool(c.get("PREDICT_BY_DEPTH", False))
-        ref_fea = self.feature_extraction(ref).float()
+        fused = fused_channels_last(self.cost_dtype, self.conv_precision)
+        ref_raw = self.feature_extraction(ref)
+        # the float32 copy of the reference features, made where something reads it: the sweep of anything but
+        # float16 features on the fused route, the context stack, PSNET_DEP_CONTEXT
+        ref_fea = None
         costs = None
         for j, target in enumerate(targets):
-            tgt_fea = self.feature_extraction(target).float()
-            if fused_channels_last(self.cost_dtype, self.conv_precision):
+            tgt_raw = self.feature_extraction(target)
+            if fused and f16_features(ref_raw, tgt_raw):
+                # MIXED_PREC: the fused sweep reads the float16 features as they come (the same bits)
+                r, t = ref_raw, tgt_raw
+            else:
+                ref_fea = ref_raw.float() if ref_fea is None else ref_fea
+                r, t = ref_fea, tgt_raw.float()
+            if fused:
                 # the sweep writes the stack's channels-last input itself: the same bits, no planar volume
-                c0 = sweep_regularize_fused(self, ref_fea.contiguous(), tgt_fea.contiguous(),
+                c0 = sweep_regularize_fused(self, r.contiguous(), t.contiguous(),
                                             pose[:, j].float().contiguous(), K4, Ki4, self.nlabel, self.mindepth,
                                             self.conv_precision, pbd)
             else:
-                cost = plane_sweep_cost(ref_fea.contiguous(), tgt_fea.contiguous(),
+                cost = plane_sweep_cost(r.contiguous(), t.contiguous(),
                                         pose[:, j].float().contiguous(), K4, Ki4, self.nlabel, self.mindepth,
                                         dtype=self.cost_dtype, predict_by_depth=pbd)
                 c0 = self.regularize(cost)
@@ -179,6 +190,8 @@ class PSNet(CostRegularization):
         if c.get("PSNET_CONTEXT", True):
             if c.get("IND_CONTEXT", False):
                 ref_fea = self.context_net(ref).float()        # PSNet.py:177-178 reassigns refimg_fea
+            elif ref_fea is None:
+                ref_fea = ref_raw.float()
             ctx = ref_fea
             # every plane through the same 2-D stack: one batch of B*L images
             planes = costs[:, 0].permute(1, 0, 2, 3).reshape(L * B, 1, h, w)
@@ -190,6 +203,7 @@ class PSNet(CostRegularization):
                                 scale=1.0 if pbd else None)
         depth = depth_head(costss.reshape(B, L, h, w).contiguous(), self.nlabel, self.mindepth, (H, W), pbd)
         if c.get("PSNET_DEP_CONTEXT", False):
+            ref_fea = ref_raw.float() if ref_fea is None else ref_fea
             up = F.interpolate(ref_fea, [H, W], mode="bilinear", align_corners=True)
             feat = torch.cat((depth.detach(), up, ref.float()), dim=1)
             return depth, self.dep_convs(feat) + depth

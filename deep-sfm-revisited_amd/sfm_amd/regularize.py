@@ -276,12 +276,24 @@ def fused_channels_last(cost_dtype, precision):
     return cost_dtype == torch.float32 and precision in _ACT_DTYPE and _lib.tune_get("sweep_fused_cl") == 1
 
 
+def f16_features(ref_fea, tgt_fea):
+    """Whether the fused route hands these features to the sweep as they come:
+    both float16 (the feature CNN's output under cfg.MIXED_PREC autocast) and
+    the library switch ``sweep_f16_feat`` at 1.  Otherwise they are widened to
+    float32 first: the same bits either way."""
+    return ref_fea.dtype == torch.float16 and tgt_fea.dtype == torch.float16 and \
+        _lib.tune_get("sweep_f16_feat") == 1
+
+
 def sweep_regularize_fused(regularizer, ref_fea, tgt_fea, pose, K4, Ki4, nlabel, min_depth, precision,
                            predict_by_depth=False):
     """Sweep + regularisation on the fused route: [B, 1, L, h, w] fp32, the
-    bits of ``regularizer(plane_sweep_cost(...), precision=precision)``."""
+    bits of ``regularizer(plane_sweep_cost(...), precision=precision)``.
+    Float16 features stay float16 (``f16_features``)."""
     if precision not in _ACT_DTYPE:
         raise ValueError(f"unknown conv precision {precision!r}")
+    if not f16_features(ref_fea, tgt_fea):
+        ref_fea, tgt_fea = ref_fea.float(), tgt_fea.float()
     x = plane_sweep_cost_channels_last(ref_fea, tgt_fea, pose, K4, Ki4, nlabel, min_depth,
                                        dtype=_ACT_DTYPE[precision], predict_by_depth=predict_by_depth)
     return CostRegularization.forward_channels_last(regularizer, x, precision=precision)

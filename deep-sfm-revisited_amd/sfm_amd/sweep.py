@@ -94,12 +94,17 @@ def plane_sweep_cost_channels_last(ref_fea, tgt_fea, pose, intrinsics4, intrinsi
     the regularisation stack reads (PSNet.py:159), bit-identical to
     ``to_channels_last(plane_sweep_cost(..., dtype=float32), dtype)`` without
     the planar volume in between (sfm_plane_sweep_cl).  Arguments as
-    ``plane_sweep_cost``."""
+    ``plane_sweep_cost``.  Features that are both float16 are read as they
+    come (sfm_plane_sweep_cl_f16: no float32 copies, the same bits as for
+    ``ref_fea.float()``, ``tgt_fea.float()``); any other dtypes are converted
+    to float32."""
     _refuse_grad(ref_fea=ref_fea, tgt_fea=tgt_fea, pose=pose, intrinsics4=intrinsics4,
                  intrinsics_inv4=intrinsics_inv4)
-    tgt = _dev_f32(tgt_fea, "tgt_fea")
+    f16_feat = ref_fea.dtype == torch.float16 and tgt_fea.dtype == torch.float16 and ref_fea.is_cuda and \
+        tgt_fea.is_cuda
+    tgt = tgt_fea.contiguous() if f16_feat else _dev_f32(tgt_fea, "tgt_fea")
     B, C, h, w = tgt.shape
-    ref = _dev_f32(ref_fea, "ref_fea")
+    ref = ref_fea.contiguous() if f16_feat else _dev_f32(ref_fea, "ref_fea")
     if tuple(ref.shape) != (B, C, h, w):
         raise RuntimeError(f"ref_fea shape {tuple(ref.shape)} != tgt_fea shape {(B, C, h, w)}")
     pose = _dev_f32(pose.reshape(B, 3, 4), "pose")
@@ -115,12 +120,13 @@ def plane_sweep_cost_channels_last(ref_fea, tgt_fea, pose, intrinsics4, intrinsi
     L = _lib.load()
     if workspace is None:
         workspace = workspace_for(B, C, h, w, tgt.device)
+    name = "sfm_plane_sweep_cl_f16" if f16_feat else "sfm_plane_sweep_cl"
     with torch.cuda.device(tgt.device):
-        rc = L.sfm_plane_sweep_cl(_lib.ptr(ref), _lib.ptr(tgt), B, C, h, w, _lib.ptr(pose), _lib.ptr(K4),
-                                  _lib.ptr(Ki4), int(nlabel), float(min_depth), 1 if predict_by_depth else 0,
-                                  _CL_CODE[dtype], _lib.ptr(out), _lib.ptr(workspace), workspace.numel(),
-                                  _lib.stream_ptr(tgt.device))
-        _lib.check(rc, "sfm_plane_sweep_cl")
+        rc = getattr(L, name)(_lib.ptr(ref), _lib.ptr(tgt), B, C, h, w, _lib.ptr(pose), _lib.ptr(K4),
+                              _lib.ptr(Ki4), int(nlabel), float(min_depth), 1 if predict_by_depth else 0,
+                              _CL_CODE[dtype], _lib.ptr(out), _lib.ptr(workspace), workspace.numel(),
+                              _lib.stream_ptr(tgt.device))
+        _lib.check(rc, name)
     return out
 
 

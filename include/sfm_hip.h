@@ -262,6 +262,32 @@ int sfm_plane_sweep_cl(const float* ref, const float* tgt, int batch, int channe
                        int out_dtype /* 0 fp32, 1 bf16, 2 f16 */,
                        void* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* sfm_plane_sweep_cl for float16 features, read as they come (the feature CNN's
+ * output under cfg.MIXED_PREC autocast, models/SFMnet.py:80, 119): no float32
+ * copy of either map, and the target is re-laid out as 16-byte channel octets,
+ * so a tap gather brings eight channels where a float32 quad brings four.
+ *   ref, tgt [dev] batch x C x h x w IEEE half, 2-byte aligned
+ * Every other argument, every check and error code as sfm_plane_sweep_cl.
+ * Contract: the result equals sfm_plane_sweep_cl on the same features widened
+ * to float32, bit for bit, for every finite or infinite feature value (half to
+ * float32 is exact, subnormals included; the tap sum and the rounding are the
+ * same float32 operations).  channels a multiple of 8, for every out_dtype,
+ * with every pair's tensors below 4 GiB take the wide-store kernel, any other
+ * shape an element-wise one: the same values.
+ *   workspace sfm_plane_sweep_workspace_bytes(batch, channels, h, w): the
+ *             octets, [B][ceil(C/8)][h*w] x 16 bytes, fit the quads' region
+ *             ([B][ceil(C/4)][h*w] x 16 bytes), so there is no query of its own.
+ * Stream-ordered, no allocation.  The switch "sweep_f16_feat" (sfm_tune_set;
+ * 0, 1; default 1; not enumerated by sfm_tune_key) is not read here: like
+ * "sweep_fused_cl" it tells the Python depth stage (sfm_amd.psnet,
+ * sfm_amd.regularize), which holds float16 features under MIXED_PREC, whether
+ * to pass them here or to widen them for sfm_plane_sweep_cl. */
+int sfm_plane_sweep_cl_f16(const void* ref, const void* tgt, int batch, int channels, int h, int w,
+                           const float* pose, const float* K4, const float* K4inv,
+                           int nlabel, float min_depth, int predict_by_depth,
+                           int out_dtype /* 0 fp32, 1 bf16, 2 f16 */,
+                           void* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The sweep section of PSNet.forward from the pose stage's outputs, in one
  * call (models/PSNet.py:130-157): the reference's tensor preparation runs in a
  * one-thread-per-pair kernel instead of ~10 ATen launches, bit for bit:

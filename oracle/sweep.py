@@ -25,10 +25,13 @@ def _pixel_grid(h, w, dtype=torch.float32):
     return torch.stack([xs, ys, torch.ones(h, w, dtype=dtype)], 0).reshape(1, 3, h * w)
 
 
-def warp_grid(depth, pose, K, Kinv, h, w):
-    """Sampling grid [B,h,w,2] in [-1,1] (out-of-range -> 2)."""
+def warp_coords(depth, pose, K, Kinv, h, w):
+    """The projected points and normalised coordinates of warp_grid before
+    out-of-range ones are pushed to 2: (X, Y, Z unclamped, xn, yn), each
+    [B, h*w], in the dtype of the inputs (float32: the oracle's own values;
+    float64 inputs give the same expressions in double)."""
     b = depth.shape[0]
-    pix = _pixel_grid(h, w).expand(b, 3, h * w).contiguous()
+    pix = _pixel_grid(h, w, depth.dtype).expand(b, 3, h * w).contiguous()
     cam = Kinv.bmm(pix) * depth.reshape(b, 1, h * w)
     proj = K.bmm(pose)
     pc = proj[:, :, :3].bmm(cam) + proj[:, :, 3:]
@@ -36,6 +39,13 @@ def warp_grid(depth, pose, K, Kinv, h, w):
     Z = pc[:, 2].clamp(min=1e-3)
     xn = 2 * (X / Z) / (w - 1) - 1
     yn = 2 * (Y / Z) / (h - 1) - 1
+    return X, Y, pc[:, 2], xn, yn
+
+
+def warp_grid(depth, pose, K, Kinv, h, w):
+    """Sampling grid [B,h,w,2] in [-1,1] (out-of-range -> 2)."""
+    b = depth.shape[0]
+    _, _, _, xn, yn = warp_coords(depth, pose, K, Kinv, h, w)
     xn = torch.where((xn > 1) | (xn < -1), torch.full_like(xn, 2.0), xn)
     yn = torch.where((yn > 1) | (yn < -1), torch.full_like(yn, 2.0), yn)
     return torch.stack([xn, yn], 2).reshape(b, h, w, 2)

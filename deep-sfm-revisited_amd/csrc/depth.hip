@@ -6,7 +6,8 @@
 //                  materialising the [B, C, L, h, w] warped volume.
 //   k_depth_head   soft-argmin head of PSNet.py:191-213: trilinear upsample of
 //                  the [B, L, h, w] cost to [L, H, W] (align_corners=False; the
-//                  plane axis keeps its size, so it is an identity), softmax over
+//                  plane axis keeps its size, so it is an identity; weights and
+//                  interpolated logits in float64), softmax over
 //                  planes, disparityregression (sum p_i (i+1)) -> depth =
 //                  MIN_DEPTH L / (disp + 1e-16), or depthregression
 //                  (sum p_i (i+1) step) * MIN_DEPTH under cfg.PREDICT_BY_DEPTH
@@ -76,38 +77,42 @@ __global__ __launch_bounds__(kCorrThreads) void k_sweep_corr(const f32x4* __rest
 
 struct HeadTaps {
   int o00, o01, o10, o11;
-  float wx0, wx1, wy0, wy1;
+  double wx0, wx1, wy0, wy1;
 };
 
 // F.interpolate(..., mode='trilinear', align_corners=False) source index and
 // weights along one axis (PyTorch's area_pixel_compute_source_index with
-// guard_index_and_lambda; identity when the sizes match)
-__device__ __forceinline__ void axis_weights(int dst, int in_size, int out_size, float ratio, int& i0, int& i1,
-                                             float& l0, float& l1) {
+// guard_index_and_lambda; identity when the sizes match).  In float64: a
+// float32 weight is off by about 1e-6, and the classify logits differ by
+// O(100) between neighbouring taps, which moved the soft-argmin by up to 2e-4
+// of the depth against the exact interpolation (tests/test_gpu_depth.py).
+__device__ __forceinline__ void axis_weights(int dst, int in_size, int out_size, double ratio, int& i0, int& i1,
+                                             double& l0, double& l1) {
   if (in_size == out_size) {
     i0 = i1 = dst;
-    l0 = 1.0f;
-    l1 = 0.0f;
+    l0 = 1.0;
+    l1 = 0.0;
     return;
   }
-  float src = ratio * ((float)dst + 0.5f) - 0.5f;
-  if (src < 0.0f) src = 0.0f;
-  i0 = min((int)floorf(src), in_size - 1);
-  l1 = fminf(fmaxf(src - (float)i0, 0.0f), 1.0f);
+  double src = ratio * ((double)dst + 0.5) - 0.5;
+  if (src < 0.0) src = 0.0;
+  i0 = min((int)floor(src), in_size - 1);
+  l1 = fmin(fmax(src - (double)i0, 0.0), 1.0);
   i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-  l0 = 1.0f - l1;
+  l0 = 1.0 - l1;
 }
 
-// interpolated cost of plane l (PyTorch's nested order: ((x00 wx0 + x01 wx1) wy0 + (x10 wx0 + x11 wx1) wy1))
-__device__ __forceinline__ float head_value(const float* __restrict__ plane, const HeadTaps& t) {
-  const float r0 = plane[t.o00] * t.wx0 + plane[t.o01] * t.wx1;
-  const float r1 = plane[t.o10] * t.wx0 + plane[t.o11] * t.wx1;
+// interpolated cost of plane l (PyTorch's nested order: ((x00 wx0 + x01 wx1) wy0 + (x10 wx0 + x11 wx1) wy1)),
+// float32 taps combined in float64
+__device__ __forceinline__ double head_value(const float* __restrict__ plane, const HeadTaps& t) {
+  const double r0 = (double)plane[t.o00] * t.wx0 + (double)plane[t.o01] * t.wx1;
+  const double r1 = (double)plane[t.o10] * t.wx0 + (double)plane[t.o11] * t.wx1;
   return r0 * t.wy0 + r1 * t.wy1;
 }
 
 // grid (ceil(W / 256), H, B); thread = output pixel
 __global__ __launch_bounds__(kHeadThreads) void k_depth_head(const float* __restrict__ cost, int L, int h, int w,
-                                                             int H, int W, float ratio_h, float ratio_w,
+                                                             int H, int W, double ratio_h, double ratio_w,
                                                              int depth_mode, float min_depth, float step,
                                                              float* __restrict__ depth) {
   const int b = blockIdx.z, Y = blockIdx.y;
@@ -121,19 +126,22 @@ __global__ __launch_bounds__(kHeadThreads) void k_depth_head(const float* __rest
   t.o10 = y1 * w + x0; t.o11 = y1 * w + x1;
   const size_t hw = (size_t)h * w;
   const float* cb = cost + (size_t)b * L * hw;
-  // softmax over planes (max, then exp(v - max)), then the weighted sum
-  float m = -INFINITY;
-  for (int l = 0; l < L; ++l) m = fmaxf(m, head_value(cb + l * hw, t));
-  float s = 0.0f, ws = 0.0f;
+  // softmax over planes (max, then exp(v - max)), then the weighted sum.  The
+  // difference to the max is formed in float64 (at logits of 1e4 a float32
+  // value carries 1e-3 of error, which decides between nearly tied planes);
+  // the exponential of the rounded difference is float32's, the sums float64.
+  double m = -INFINITY;
+  for (int l = 0; l < L; ++l) m = fmax(m, head_value(cb + l * hw, t));
+  double s = 0.0, ws = 0.0;
   for (int l = 0; l < L; ++l) {
-    const float e = expf(head_value(cb + l * hw, t) - m);
+    const double e = (double)expf((float)(head_value(cb + l * hw, t) - m));
     s = s + e;
-    ws = ws + e * ((float)(l + 1) * step);
+    ws = ws + e * (double)((float)(l + 1) * step);
   }
-  const float reg = ws * (1.0f / s);      // sum_i p_i v_i with p_i = e_i * (1/s)
+  const double reg = ws / s;              // sum_i p_i v_i
   float out;
-  if (depth_mode) out = reg * min_depth;                          // PSNet.py:209-210
-  else out = (min_depth * (float)L) / (reg + 1e-16f);             // PSNet.py:212-213
+  if (depth_mode) out = (float)(reg * (double)min_depth);                               // PSNet.py:209-210
+  else out = (float)(((double)min_depth * (double)L) / (reg + 1e-16));                  // PSNet.py:212-213
   depth[((size_t)b * H + Y) * W + X] = out;
 }
 
@@ -225,8 +233,8 @@ int sfm_depth_head(const float* cost, int batch, int nlabel, int h, int w, int H
   SFM_REQUIRE((int64_t)nlabel * h * w < ((int64_t)1 << 31), "cost volume too large");
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps("depth_head", s);
-  // area_pixel_compute_scale: (float)input_size / output_size
-  const float ratio_h = (float)h / (float)H, ratio_w = (float)w / (float)W;
+  // area_pixel_compute_scale in float64: input_size / output_size
+  const double ratio_h = (double)h / (double)H, ratio_w = (double)w / (double)W;
   hipLaunchKernelGGL(k_depth_head, dim3((W + kHeadThreads - 1) / kHeadThreads, H, batch), dim3(kHeadThreads), 0, s,
                      cost, nlabel, h, w, H, W, ratio_h, ratio_w, depth_mode, min_depth,
                      depth_mode ? depth_step : 1.0f, depth);

@@ -132,6 +132,7 @@ const TuneKey kTuneKeys[] = {
     {"score_mf_blocks_per_cu", &sfm::Tuning::score_mf_blocks_per_cu, [](int v) { return v >= 1 && v <= 8; }},
     {"score_interleave", &sfm::Tuning::score_interleave, v_01},
     {"conv_rolling", &sfm::Tuning::conv_rolling, v_01},
+    {"conv_planes", &sfm::Tuning::conv_planes, [](int v) { return v == 0 || v == 4 || v == 8 || v == 16 || v == 32; }},
     {"score_precision", &sfm::Tuning::score_precision, [](int v) { return v == 64 || v == 32 || v == 16; }},
     {"score_lowp_template", &sfm::Tuning::score_lowp_template, v_01},
 };

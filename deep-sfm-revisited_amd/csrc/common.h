@@ -50,6 +50,7 @@ struct Tuning {
   int score_lowp_template = 0;   // 32 / 16: 0 = E and every operation held in T (this build's variant);
                                  // 1 = the literal ComputeError<T> with double Ematrix (double products)
   int conv_rolling = 1;          // 1: cin-32 conv layers roll along the planes (k_conv3r); 0: k_conv3
+  int conv_planes = 0;           // k_conv3r planes per block: 4, 8, 16, 32; 0: by grid size (conv3_lp)
   int score_ref_rider = 1;       // the cost volume's reference half written by the one-sided scorer's first
                                  // launch (sfm_score_ref_job; score_mf2.h); 0: the sweep writes both halves
   int sweep_fused_cl = 1;        // read by the Python depth stage only (sfm_amd.regularize.fused_channels_last): 1: the

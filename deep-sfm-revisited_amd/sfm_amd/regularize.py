@@ -33,6 +33,10 @@ from .sweep import plane_sweep_cost, plane_sweep_cost_channels_last, quarter_int
 
 _ACT_DTYPE = {"fp32": torch.float32, "fp32x3": torch.float32, "fp16": torch.float16, "bf16": torch.bfloat16}
 
+# sfm_conv3_f32x3 with a range flag re-runs a layer as sfm_conv3_f32 when its largest |activation| is below
+# this (kX3AmaxMin in csrc/regularize.hip): there the split's low halves are subnormal f16
+FP32X3_MIN_AMAX = 2.0 ** -3
+
 
 def weight_exponent(w):
     """sfm_conv3_f32x3's weight scale: the power of two 2^e with 2^e max|w| in
@@ -240,9 +244,9 @@ class CostRegularization(nn.Module):
             stream = _lib.stream_ptr(dev)
             bufs = [torch.empty((B, L, h, w, 32), dtype=adt, device=dev) for _ in range(3)]
             out = torch.empty((B, 1, L, h, w), dtype=torch.float32, device=dev)
-            # fp32x3: one range flag per layer -- a layer whose input leaves the
-            # f16 range is re-run by sfm_conv3_f32 inside the same call, stream-ordered
-            flags = torch.empty(len(packed), dtype=torch.int32, device=dev) if precision == "fp32x3" else None
+            # fp32x3: one range flag (two words) per layer -- a layer whose input leaves the f16 range, or
+            # stays below FP32X3_MIN_AMAX, is re-run by sfm_conv3_f32 inside the same call, stream-ordered
+            flags = torch.empty(2 * len(packed), dtype=torch.int32, device=dev) if precision == "fp32x3" else None
             cur, keep = x, None           # keep: the block input of a residual pair (cost0)
             for li, lay in enumerate(packed):
                 if lay["cout"] == 1:
@@ -253,7 +257,7 @@ class CostRegularization(nn.Module):
                 if precision == "fp32x3":
                     rc = x3(_lib.ptr(cur), B, lay["cin"], L, h, w, _lib.ptr(lay["w"]), lay["wexp"],
                             _lib.ptr(lay["scale"]), _lib.ptr(lay["bias"]), None if res is None else _lib.ptr(res),
-                            1 if lay["relu"] else 0, lay["cout"], _lib.ptr(dst), flags[li].data_ptr(), stream)
+                            1 if lay["relu"] else 0, lay["cout"], _lib.ptr(dst), flags[2 * li].data_ptr(), stream)
                 else:
                     rc = conv(_lib.ptr(cur), B, lay["cin"], L, h, w, _lib.ptr(lay["w"]), _lib.ptr(lay["scale"]),
                               _lib.ptr(lay["bias"]), None if res is None else _lib.ptr(res), 1 if lay["relu"] else 0,

@@ -530,14 +530,21 @@ int sfm_conv3_f32(const float* in, int batch, int cin, int depth, int h, int w, 
  * so that 2^wexp max|w| < 2^15).  Replaces the same Conv3d layers
  * (models/PSNet.py:79-102, applied at 159-165).
  * The split is valid while every input activation is within the f16 range
- * (|x| <= 65504; the reference's fp32 Conv3d has no such limit).  range_flag
- * [dev] 4 bytes or NULL: when given, the call zeroes it, the kernel sets it to
- * 1 if any input activation exceeds 65504 (or is infinite), and a second,
- * stream-ordered launch of the sfm_conv3_f32 layer overwrites out in that case
- * (its blocks exit at once otherwise) -- the layer's result is then exactly
- * sfm_conv3_f32's.  NULL: no check (the caller guarantees the range).  Below
- * 2^-14 the f16 terms are subnormal: such activations keep an absolute error
- * <= 2^-25 per product term, not a relative one. */
+ * (|x| <= 65504; the reference's fp32 Conv3d has no such limit), and it is
+ * as precise as stated while x_lo = f16(x - f16(x)), ~2^-11 |x|, is a normal
+ * f16: for |x| >= 2^-3.  Below 2^-3 x_lo is subnormal and the product keeps an
+ * absolute error of 2^-25 |w| per term, not a relative one: the layer's error
+ * doubles with every halving of the activations' scale.  range_flag [dev] two
+ * int32 words (8 bytes, 4-byte aligned) or NULL: when given, the call zeroes
+ * both, the kernel sets word 0 to 1 if any input activation exceeds 65504 (or
+ * is infinite) and raises word 1 to the bit pattern of the layer's largest
+ * finite-or-infinite |activation| (NaNs are skipped), and a second,
+ * stream-ordered launch of the sfm_conv3_f32 layer overwrites out when word 0
+ * is set or that maximum is below 2^-3 (its blocks exit at once otherwise) --
+ * the layer's result is then exactly sfm_conv3_f32's, at any activation scale.
+ * The maximum is the layer's: a layer of tiny activations with a few large
+ * ones is not re-run, and its error stays small relative to its largest
+ * outputs only.  NULL: no check (the caller guarantees both sides). */
 int sfm_conv3_f32x3(const float* in, int batch, int cin, int depth, int h, int w, const float* weights, int wexp,
                     const float* scale, const float* bias, const float* residual, int relu, int cout, float* out,
                     int* range_flag, void* stream);
@@ -626,6 +633,8 @@ int sfm_to_channels_last_f32(const void* in, int in_dtype, int batch, int channe
  *                                     a block (2, measured 2-6 % slower), speculated
  *                                     fallback bisection; same bits as k_roots (0)
  *     "conv_rolling"          0, 1    rolling-plane Conv3d for cin 32 (1; same bits)
+ *     "conv_planes"           0,4,8,  output planes per block of the rolling-plane
+ *                             16,32   Conv3d (0, default: by grid size; same bits)
  *
  *   results MAY change (sweep outputs by FMA rounding only):
  *     "sweep_flat"            0..3    2 (default): k_sweep_tile, 1: k_sweep_flat,

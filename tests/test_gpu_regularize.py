@@ -392,10 +392,10 @@ def test_conv_layer_f32x3_out_of_f16_range(cuda, peak, rerun):
     wt = torch.randn(cout, cin, 3, 3, 3, generator=g) * 0.1
     scale = 0.5 + torch.rand(cout, generator=g)
     bias = 0.3 * torch.randn(cout, generator=g)
-    flag = torch.full((1,), 7, dtype=torch.int32, device=cuda)
+    flag = torch.full((2,), 7, dtype=torch.int32, device=cuda)     # two words: out of range, largest activation
     got = _conv_f32x3(cuda, x, wt, scale, bias, None, True, cout, flag=flag)
     ref32 = _conv_f32(cuda, x, wt, scale, bias, None, True, cout)
-    assert int(flag.item()) == (1 if rerun else 0)
+    assert int(flag[0].item()) == (1 if rerun else 0)
     if rerun:
         assert torch.equal(torch.isnan(got), torch.isnan(ref32))
         m = ~torch.isnan(ref32)

@@ -117,5 +117,6 @@ def test_f16_feature_switch():
         assert _lib.tune_get("sweep_f16_feat") == 1
     finally:
         _lib.tune("sweep_f16_feat", old)
-    # a switch, not a launch-shape knob: sfm_tune_key does not enumerate it, and the enumerated set is unchanged
-    assert "sweep_f16_feat" not in _lib.tune_keys() and len(_lib.tune_keys()) == 31
+    # a switch, not a launch-shape knob: sfm_tune_key does not enumerate it, and the enumerated set is the
+    # launch-shape and scoring knobs (32 since conv_planes)
+    assert "sweep_f16_feat" not in _lib.tune_keys() and len(_lib.tune_keys()) == 32

@@ -11,7 +11,8 @@ and runs its forward with the hot path on libsfm_hip:
                       channels-last for the next stage                 sfm_plane_sweep_cl (HIP); float16 features
                       (cfg.MIXED_PREC) read as they come               sfm_plane_sweep_cl_f16 (HIP)
   dres0..4, classify  3-D cost regularisation (PSNet.py:79-102, 159-165)  sfm_conv3_* (HIP MFMA)
-  convs               per-plane context CNN (PSNET_CONTEXT, 175-192)   torch (MIOpen)
+  convs               per-plane context CNN (PSNET_CONTEXT, 175-192)   sfm_conv2_* (HIP MFMA) under float16 autocast
+                      in eval mode (``context_precision``); else       torch (MIOpen)
   head                trilinear up, softmax, disparity regression     sfm_depth_head (HIP)
   dep_convs           full-resolution depth refinement (PSNET_DEP_CONTEXT, 218-225)  torch (MIOpen)
 
@@ -25,9 +26,17 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .config import cfg as _default_cfg
+from .context import context_refine, stock_layout
 from .depth import depth_head
 from .regularize import CostRegularization, f16_features, fused_channels_last, sweep_regularize_fused
 from .sweep import plane_sweep_cost, quarter_intrinsics
+
+
+def _autocast_gpu_dtype():
+    """torch.get_autocast_gpu_dtype(), by its newer name where torch has it."""
+    if hasattr(torch, "get_autocast_dtype"):
+        return torch.get_autocast_dtype("cuda")
+    return torch.get_autocast_gpu_dtype()
 
 
 def _conv_bn(cin, cout, k, stride, pad, dilation):
@@ -118,10 +127,17 @@ class PSNet(CostRegularization):
     f16 split on the f16 matrix cores: within the float64 fixture's depth bars
     at 3x the speed of "fp32", the f32-MFMA path, which stays selectable) or
     "fp16"; "bf16" is the fastest opt-in path;
-    ``cost_dtype`` the sweep volume's storage."""
+    ``cost_dtype`` the sweep volume's storage.  ``context_precision`` selects
+    how the per-plane context stack ``convs`` runs (PSNet.py:175-190): "torch"
+    (nn.Conv2d), "fp16" / "bf16" (``sfm_amd.context.context_refine``, eval
+    mode only) or "auto" (default), which takes the "fp16" route exactly where
+    torch would compute these convolutions in float16 anyway -- eval mode,
+    float16 CUDA autocast active at the call (what SFMnet.forward sets under
+    cfg.MIXED_PREC), no forward (pre-)hooks on ``convs``, the stock
+    33-channel stack -- and "torch" everywhere else."""
 
     def __init__(self, nlabel, mindepth=None, cfg=None, feature_fn=None, cost_dtype=torch.float32,
-                 conv_precision="auto"):
+                 conv_precision="auto", context_precision="auto"):
         super().__init__(64)
         c = _default_cfg if cfg is None else cfg
         if c.get("COST_BY_COLOR", False) or c.get("COST_BY_COLOR_WITH_FEAT", False):
@@ -135,6 +151,9 @@ class PSNet(CostRegularization):
         if conv_precision not in ("fp32", "fp32x3", "fp16", "bf16"):
             raise ValueError(f"unknown conv precision {conv_precision!r}")
         self.conv_precision = conv_precision
+        if context_precision not in ("auto", "torch", "fp16", "bf16"):
+            raise ValueError(f"unknown context precision {context_precision!r}")
+        self.context_precision = context_precision
         self.feature_extraction = FeatureExtraction() if feature_fn is None else feature_fn
         if c.get("IND_CONTEXT", False):
             self.context_net = FeatureExtraction()
@@ -151,6 +170,25 @@ class PSNet(CostRegularization):
 
     def regularize(self, cost):
         return CostRegularization.forward(self, cost, precision=self.conv_precision)
+
+    def context_route(self, device=None):
+        """How the context stack runs at this call: "torch", "fp16" or "bf16"
+        (see ``context_precision``)."""
+        p = self.context_precision
+        if p == "torch":
+            return p
+        if p in ("fp16", "bf16"):
+            if self.training:
+                raise RuntimeError(f"context_precision={p!r} folds BatchNorm2d and has no backward: eval mode only")
+            return p
+        on_gpu = device is not None and torch.device(device).type == "cuda"
+        if self.training or not on_gpu or not torch.is_autocast_enabled() or _autocast_gpu_dtype() != torch.float16:
+            return "torch"
+        # the HIP route calls no module, so it is taken only where self.convs(x) would run the stock stack and
+        # nothing else (the rule psnet_depth applies to the fused sweep)
+        if self.convs._forward_hooks or self.convs._forward_pre_hooks or not stock_layout(self.convs):
+            return "torch"
+        return "fp16"
 
     def forward(self, ref, targets, pose, intrinsics, intrinsics_inv, pose_gt=None, depth_gt=None, E_mat=None):
         c = self.cfg
@@ -187,7 +225,13 @@ class PSNet(CostRegularization):
         B, _, L, h, w = costs.shape
         H, W = ref.shape[2], ref.shape[3]
         costss = costs
-        if c.get("PSNET_CONTEXT", True):
+        route = self.context_route(costs.device) if c.get("PSNET_CONTEXT", True) else None
+        if route in ("fp16", "bf16"):
+            # the stack on libsfm_hip: the features in whatever dtype they arrive (no float32 copy), the planes
+            # b-major, so the result is already the [B, L, h, w] volume the head reads
+            ctx = self.context_net(ref) if c.get("IND_CONTEXT", False) else ref_raw    # PSNet.py:177-178
+            costss = context_refine(self.convs, ctx, costs.float(), precision=route)
+        elif route == "torch":
             if c.get("IND_CONTEXT", False):
                 ref_fea = self.context_net(ref).float()        # PSNet.py:177-178 reassigns refimg_fea
             elif ref_fea is None:

@@ -555,6 +555,49 @@ int sfm_conv3_f32x3(const float* in, int batch, int cin, int depth, int h, int w
 int sfm_to_channels_last_f32(const void* in, int in_dtype, int batch, int channels, int64_t plane, float* out,
                              void* stream);
 
+/* One stage of PSNet's per-plane context stack (convtext,
+ * models/PSNet.py:17-26; the seven stages 64-71; applied at 190): a 3 x 3,
+ * stride 1, dilated Conv2d with "same" zero padding (pad = dilation), its
+ * optional BatchNorm2d folded (eval mode), on v_mfma_f32_32x32x16_f16 with
+ * fp32 accumulation:
+ *   out = [relu](conv3x3(in) * scale[co] + bias[co])
+ *   in [dev] images x h x w x cin float16 (channels-last), cin 32, 64, 96 or 128;
+ *   weights [dev] 9 x cout_pad x cin float16, tap = kh*3 + kw, cout_pad = cout
+ *     rounded up to 32 (rows beyond cout zero);
+ *   dilation 1..16;
+ *   scale, bias [dev] cout_pad float32 (BatchNorm folded; 1 / 0 for a plain conv);
+ *   cout 32, 64, 96 or 128: out [dev] images x h x w x cout float16, rounded
+ *     once (to nearest even) after the ReLU; residual1 must be NULL;
+ *   cout 1: out [dev] images x h x w float32 =
+ *     f16round([relu](acc * scale + bias)) + residual1[pixel] -- the float16
+ *     value torch's autocast gives convs(x), then the float32 "+ plane" of
+ *     PSNet.py:190; residual1 [dev] images x h x w float32 or NULL.
+ * Every pointer 16-byte aligned; out aliases no input. */
+int sfm_conv2_f16(const void* in, int images, int cin, int h, int w, const void* weights, int cout, int dilation,
+                  const float* scale, const float* bias, int relu, const float* residual1, void* out, void* stream);
+
+/* sfm_conv2_f16 with every 16-bit operand bfloat16 (v_mfma_f32_32x32x16_bf16),
+ * the cout 1 value rounded to bfloat16 before the add: the same context stage
+ * (models/PSNet.py:17-26, 64-71, 190) as the opt-in 8-bit-mantissa path. */
+int sfm_conv2_bf16(const void* in, int images, int cin, int h, int w, const void* weights, int cout, int dilation,
+                   const float* scale, const float* bias, int relu, const float* residual1, void* out, void* stream);
+
+/* The context stack's first-stage input (models/PSNet.py:17-26, 64-71, 190:
+ * cat(ref features, cost plane) per plane) for planes l0 .. l0+nl-1 of every
+ * pair, channels-last and padded to 64 channels:
+ *   ctx [dev] batch x channels x h x w float32, channels == 32;
+ *   planes [dev] batch x nlabel x h x w float32;
+ *   out [dev] batch x nl x h x w x 64 float16 (round to nearest even):
+ *     channels 0..31 ctx[b] (the same for every plane), channel 32
+ *     planes[b][l0 + l], channels 33..63 zero.  Images are b-major, so the
+ *     cout 1 stage's output is batch x nl x h x w, sfm_depth_head's layout. */
+int sfm_context_pack_f16(const float* ctx, const float* planes, int batch, int nlabel, int l0, int nl, int channels,
+                         int h, int w, void* out, void* stream);
+
+/* sfm_context_pack_f16 writing bfloat16 (models/PSNet.py:17-26, 64-71, 190). */
+int sfm_context_pack_bf16(const float* ctx, const float* planes, int batch, int nlabel, int l0, int nl, int channels,
+                          int h, int w, void* out, void* stream);
+
 /* Tuning knobs (process-wide; every key, its accepted values and default):
  *
  *   launch shape only -- outputs are bit-identical for every value:

@@ -245,6 +245,73 @@ __global__ __launch_bounds__(256) void k_context_pack(const float* __restrict__ 
   *reinterpret_cast<uint4*>(out + pixel * 64 + chunk * 8) = v;
 }
 
+// The first input of the full-resolution refinement stack dep_convs
+// (models/PSNet.py:218-221) for pairs b0 .. b0+nb-1: [nb][H][W][64], channel 0
+// depth, 1..32 the [h][w] features upsampled bilinearly to H x W
+// (align_corners=True), 33..35 the image, 36..63 zero -- the order of the
+// reference's cat((depth, up_feat, ref)).  One thread per (pixel, 8-channel
+// chunk) as in k_context_pack: 16-byte stores, 128 contiguous bytes per pixel.
+// Chunk 0 holds the depth and features 0..6, chunks 1..3 features 8k-1 ..
+// 8k+6, chunk 4 feature 31 and the image, chunks 5..7 zeros.  The features are
+// read in their own type T; the low-resolution map is re-read from cache.
+// The interpolation is torch's upsample_bilinear2d term by term (no
+// contraction: the file is built with -ffp-contract=off), evaluated in
+// float64: in fp32 the rounding of src = scale * dst alone (2^-24 src, 1e-6 at
+// the right edge of a KITTI row) is several float16 steps wherever the four
+// terms cancel to a small value.  In float64 the sum is the exact one to 1e-16,
+// so the single rounding to the 16-bit type (through float32, as torch converts
+// a float64 tensor) is the only one.
+template <typename T> __device__ __forceinline__ double feat_to_d(T v);
+template <> __device__ __forceinline__ double feat_to_d<float>(float v) { return (double)v; }
+template <> __device__ __forceinline__ double feat_to_d<_Float16>(_Float16 v) { return (double)(float)v; }
+template <> __device__ __forceinline__ double feat_to_d<__bf16>(__bf16 v) { return (double)(float)v; }
+
+template <bool F16, typename T>
+__global__ __launch_bounds__(256) void k_dep_pack(const float* __restrict__ depth, const T* __restrict__ feat,
+                                                  const float* __restrict__ image, int b0, int h, int w, int H, int W,
+                                                  double sy, double sx, int nbx, unsigned short* __restrict__ out) {
+  const int img = blockIdx.x / nbx;
+  const int i = (blockIdx.x - img * nbx) * 256 + threadIdx.x;
+  const int HW = H * W;
+  if (i >= HW * 8) return;
+  const int chunk = i & 7, p = i >> 3;
+  const int y = p / W, x = p - y * W;
+  const int b = b0 + img;
+  unsigned short s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (chunk < 5) {
+    const double fy = sy * (double)y, fx = sx * (double)x;
+    const int y0 = min((int)fy, h - 1), x0 = min((int)fx, w - 1);
+    const int y1 = y0 + (y0 < h - 1), x1 = x0 + (x0 < w - 1);
+    const double ly1 = fy - (double)y0, lx1 = fx - (double)x0;
+    const double ly0 = 1.0 - ly1, lx0 = 1.0 - lx1;
+    const int o00 = y0 * w + x0, o01 = y0 * w + x1, o10 = y1 * w + x0, o11 = y1 * w + x1;
+    const int hw = h * w;
+    const T* f = feat + (int64_t)b * 32 * hw;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int c = chunk * 8 + j - 1;   // slot j of this chunk is feature c
+      if (c >= 0 && c < 32) {
+        const T* fc = f + (int64_t)c * hw;
+        const double v = ly0 * (lx0 * feat_to_d<T>(fc[o00]) + lx1 * feat_to_d<T>(fc[o01])) +
+                         ly1 * (lx0 * feat_to_d<T>(fc[o10]) + lx1 * feat_to_d<T>(fc[o11]));
+        s[j] = ActCvt<F16>::from_f((float)v);
+      }
+    }
+    if (chunk == 0) s[0] = ActCvt<F16>::from_f(depth[(int64_t)b * HW + p]);
+    if (chunk == 4) {
+      const float* im = image + (int64_t)b * 3 * HW + p;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) s[1 + k] = ActCvt<F16>::from_f(im[(int64_t)k * HW]);
+    }
+  }
+  uint4 v;
+  v.x = s[0] | ((unsigned)s[1] << 16);
+  v.y = s[2] | ((unsigned)s[3] << 16);
+  v.z = s[4] | ((unsigned)s[5] << 16);
+  v.w = s[6] | ((unsigned)s[7] << 16);
+  *reinterpret_cast<uint4*>(out + ((int64_t)img * HW + p) * 64 + chunk * 8) = v;
+}
+
 template <bool F16, int NG>
 void launch_conv2(hipStream_t s, const void* in, int images, int cin, int h, int w, const void* weights, int cout,
                   int dilation, const float* scale, const float* bias, int relu, const float* residual1, void* out) {
@@ -308,6 +375,39 @@ int context_pack(const float* ctx, const float* planes, int batch, int nlabel, i
   return SFM_OK;
 }
 
+template <bool F16>
+int dep_context_pack(const float* depth, const void* feat, int feat_dtype, const float* image, int batch, int b0,
+                     int nb, int channels, int h, int w, int H, int W, void* out, void* stream) {
+  SFM_REQUIRE(depth && feat && image && out, "null pointer argument");
+  SFM_REQUIRE(feat_dtype >= 0 && feat_dtype <= 2, "feat_dtype must be 0 (float32), 1 (bfloat16) or 2 (float16)");
+  SFM_REQUIRE(channels == 32, "the refinement stack's first layer takes 1 depth + 32 feature + 3 image channels");
+  SFM_REQUIRE(batch >= 1 && h >= 1 && w >= 1 && H >= 1 && W >= 1, "invalid refinement shape");
+  SFM_REQUIRE(b0 >= 0 && nb >= 1 && b0 <= batch - nb, "pair range outside the batch");
+  SFM_REQUIRE((int64_t)h * w < ((int64_t)1 << 28), "feature map too large");
+  SFM_REQUIRE((int64_t)H * W < ((int64_t)1 << 28), "image too large");
+  SFM_REQUIRE(((uintptr_t)out & 15) == 0, "output must be 16-byte aligned");
+  const int nbx = (int)(((int64_t)H * W * 8 + 255) / 256);
+  SFM_REQUIRE((int64_t)nbx * nb < ((int64_t)1 << 31), "refinement pack grid too large");
+  // torch's area_pixel_compute_scale for align_corners=True, in float64
+  const double sy = H > 1 ? (double)(h - 1) / (double)(H - 1) : 0.0;
+  const double sx = W > 1 ? (double)(w - 1) / (double)(W - 1) : 0.0;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps("dep_context_pack", s);
+  const dim3 grid((unsigned)(nbx * nb)), block(256);
+  unsigned short* o = (unsigned short*)out;
+  if (feat_dtype == 0)
+    hipLaunchKernelGGL((k_dep_pack<F16, float>), grid, block, 0, s, depth, (const float*)feat, image, b0, h, w, H, W,
+                       sy, sx, nbx, o);
+  else if (feat_dtype == 1)
+    hipLaunchKernelGGL((k_dep_pack<F16, __bf16>), grid, block, 0, s, depth, (const __bf16*)feat, image, b0, h, w, H,
+                       W, sy, sx, nbx, o);
+  else
+    hipLaunchKernelGGL((k_dep_pack<F16, _Float16>), grid, block, 0, s, depth, (const _Float16*)feat, image, b0, h, w,
+                       H, W, sy, sx, nbx, o);
+  SFM_LAUNCHED();
+  return SFM_OK;
+}
+
 }  // namespace
 }  // namespace sfm
 
@@ -333,6 +433,16 @@ int sfm_context_pack_f16(const float* ctx, const float* planes, int batch, int n
 int sfm_context_pack_bf16(const float* ctx, const float* planes, int batch, int nlabel, int l0, int nl, int channels,
                           int h, int w, void* out, void* stream) {
   return context_pack<false>(ctx, planes, batch, nlabel, l0, nl, channels, h, w, out, stream);
+}
+
+int sfm_dep_context_pack_f16(const float* depth, const void* feat, int feat_dtype, const float* image, int batch,
+                             int b0, int nb, int channels, int h, int w, int H, int W, void* out, void* stream) {
+  return dep_context_pack<true>(depth, feat, feat_dtype, image, batch, b0, nb, channels, h, w, H, W, out, stream);
+}
+
+int sfm_dep_context_pack_bf16(const float* depth, const void* feat, int feat_dtype, const float* image, int batch,
+                              int b0, int nb, int channels, int h, int w, int H, int W, void* out, void* stream) {
+  return dep_context_pack<false>(depth, feat, feat_dtype, image, batch, b0, nb, channels, h, w, H, W, out, stream);
 }
 
 }  // extern "C"

@@ -133,6 +133,12 @@ _SIGS = [
     ("sfm_context_pack_bf16", ctypes.c_int,
      [_c_dp, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
       _c_dp, _c_dp]),
+    ("sfm_dep_context_pack_f16", ctypes.c_int,
+     [_c_dp, _c_dp, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+      ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp]),
+    ("sfm_dep_context_pack_bf16", ctypes.c_int,
+     [_c_dp, _c_dp, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+      ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp]),
     ("sfm_score_essentials_workspace_bytes", ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     ("sfm_score_essentials", ctypes.c_int,
      [_c_dp, ctypes.c_int64, _i64p, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.c_double, _c_dp, _c_dp,

@@ -14,6 +14,14 @@ in eval mode, ReLU and the final fp32 "+ plane" fused into the epilogue --
 the precision torch computes these convolutions at under ``cfg.MIXED_PREC``
 autocast (SFMnet.py:164).  There is no PyTorch fallback: without
 libsfm_hip.so or a GPU the call raises.
+
+``dep_context_refine`` runs the second stack of the same plan, ``dep_convs``
+(PSNet.py:53-61, 218-222, cfg.PSNET_DEP_CONTEXT), at full image resolution:
+
+    depth_out = dep_convs(cat(depth, upsample(refimg_fea), ref)) + depth
+
+as one ``sfm_dep_context_pack_*`` (the bilinear upsample fused in) and the same
+seven ``sfm_conv2_*`` launches per chunk of pairs.
 """
 import weakref
 
@@ -244,3 +252,84 @@ def context_refine(convs, ctx, costs, precision="fp16", max_scratch_bytes=1 << 3
             if not whole:
                 out[:, l0:l0 + nl].copy_(last)
     return out.view(B, 1, L, h, w)
+
+
+# --- the full-resolution refinement stack dep_convs (PSNet.py:53-61, 218-222) ------
+_FEAT_DTYPE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}      # sfm_dep_context_pack_*'s feat_dtype
+
+
+def dep_stock_layout(dep_convs):
+    """Whether ``dep_convs`` is a stack ``dep_context_refine`` runs: stages
+    the kernels take, 36 input channels (depth + 32 features + the image),
+    one output."""
+    try:
+        st = _stages(dep_convs)
+    except ContextStackError:
+        return False
+    return st[0][0].in_channels == 36 and st[-1][0].out_channels == 1 and len(st) >= 2
+
+
+def pairs_per_chunk(batch, H, W, max_scratch_bytes):
+    """The most pairs whose two 128-channel full-resolution ping-pong buffers
+    fit ``max_scratch_bytes``; at least one, at most batch."""
+    per_pair = 2 * H * W * 128 * 2
+    return max(1, min(int(batch), int(max_scratch_bytes) // per_pair))
+
+
+def dep_context_refine(dep_convs, depth, feat, image, precision="fp16", max_scratch_bytes=1 << 30):
+    """``dep_convs(cat(depth, upsample(feat), image)) + depth``
+    (PSNet.py:218-221): depth [B, 1, H, W] fp32, feat [B, 32, h, w] float16,
+    bfloat16 or float32 (read as it is), image [B, 3, H, W] -> [B, 1, H, W]
+    fp32.  One ``sfm_dep_context_pack_*`` (the bilinear align_corners=True
+    upsample fused in) and the stack's ``sfm_conv2_*`` launches per chunk of
+    ``pairs_per_chunk`` whole pairs; the result does not depend on the
+    chunking.  No PyTorch fallback: CPU tensors raise."""
+    if precision not in _ACT_DTYPE:
+        raise ValueError(f"unknown context precision {precision!r}")
+    for t, n in ((depth, "depth"), (feat, "feat"), (image, "image")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise RuntimeError(f"dep_context_refine needs device tensors (HIP path, no CPU fallback): {n}")
+    if depth.dim() != 4 or depth.shape[1] != 1 or depth.dtype != torch.float32:
+        raise RuntimeError("depth must be [B, 1, H, W] float32")
+    B, _, H, W = depth.shape
+    if feat.dim() != 4 or feat.shape[0] != B or feat.shape[1] != 32 or feat.dtype not in _FEAT_DTYPE:
+        raise RuntimeError(f"feat must be [{B}, 32, h, w] float16, bfloat16 or float32")
+    if tuple(image.shape) != (B, 3, H, W) or not image.is_floating_point():
+        raise RuntimeError(f"image must be [{B}, 3, {H}, {W}] floating point")
+    if not dep_stock_layout(dep_convs):
+        _stages(dep_convs)      # raises the named reason, if that is it
+        raise ContextStackError("the refinement stack must take 36 channels and end in one")
+    h, w = feat.shape[2:]
+    dev = depth.device
+    packed = pack_context_stack(dep_convs, dev, precision)
+    adt = _ACT_DTYPE[precision]
+    lib = _lib.load()
+    pack = getattr(lib, "sfm_dep_context_pack_" + _SUFFIX[precision])
+    conv = getattr(lib, "sfm_conv2_" + _SUFFIX[precision])
+    depth = depth.detach().contiguous()
+    feat = feat.detach().contiguous()
+    image = image.detach().float().contiguous()
+    nb_max = pairs_per_chunk(B, H, W, max_scratch_bytes)
+    out = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        stream = _lib.stream_ptr(dev)
+        bufs = [torch.empty(nb_max * H * W * 128, dtype=adt, device=dev) for _ in range(2)]
+        for b0 in range(0, B, nb_max):
+            nb = min(nb_max, B - b0)
+            whole = nb == B
+            # a chunk's slice of depth is contiguous; the last stage writes a buffer of its own, 16-byte aligned
+            last = out if whole else torch.empty((nb, H, W), dtype=torch.float32, device=dev)
+            _lib.check(pack(_lib.ptr(depth), _lib.ptr(feat), _FEAT_DTYPE[feat.dtype], _lib.ptr(image), B, b0, nb, 32,
+                            h, w, H, W, _lib.ptr(bufs[0]), stream), "sfm_dep_context_pack")
+            cur = 0
+            for lay in packed:
+                final = lay["cout"] == 1
+                dst = last if final else bufs[1 - cur]
+                rc = conv(_lib.ptr(bufs[cur]), nb, lay["cin_pad"], H, W, _lib.ptr(lay["w"]), lay["cout"],
+                          lay["dilation"], _lib.ptr(lay["scale"]), _lib.ptr(lay["bias"]), 1 if lay["relu"] else 0,
+                          _lib.ptr(depth[b0:b0 + nb]) if final else None, _lib.ptr(dst), stream)
+                _lib.check(rc, "sfm_conv2")
+                cur = 1 - cur
+            if not whole:
+                out[b0:b0 + nb, 0].copy_(last)
+    return out

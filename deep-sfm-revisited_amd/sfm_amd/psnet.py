@@ -14,7 +14,9 @@ and runs its forward with the hot path on libsfm_hip:
   convs               per-plane context CNN (PSNET_CONTEXT, 175-192)   sfm_conv2_* (HIP MFMA) under float16 autocast
                       in eval mode (``context_precision``); else       torch (MIOpen)
   head                trilinear up, softmax, disparity regression     sfm_depth_head (HIP)
-  dep_convs           full-resolution depth refinement (PSNET_DEP_CONTEXT, 218-225)  torch (MIOpen)
+  dep_convs           full-resolution depth refinement (PSNET_DEP_CONTEXT, 218-225): bilinear upsample + cat
+                      sfm_dep_context_pack_* (HIP), the stack      sfm_conv2_* (HIP MFMA) under float16 autocast
+                      in eval mode (``dep_context_precision``); else   torch (MIOpen)
 
 The 2-D CNNs are outside the measured path (feature CNN and
 context networks are out of scope); they are plain torch modules here so the
@@ -26,7 +28,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .config import cfg as _default_cfg
-from .context import context_refine, stock_layout
+from .context import context_refine, dep_context_refine, dep_stock_layout, stock_layout
 from .depth import depth_head
 from .regularize import CostRegularization, f16_features, fused_channels_last, sweep_regularize_fused
 from .sweep import plane_sweep_cost, quarter_intrinsics
@@ -134,10 +136,16 @@ class PSNet(CostRegularization):
     torch would compute these convolutions in float16 anyway -- eval mode,
     float16 CUDA autocast active at the call (what SFMnet.forward sets under
     cfg.MIXED_PREC), no forward (pre-)hooks on ``convs``, the stock
-    33-channel stack -- and "torch" everywhere else."""
+    33-channel stack -- and "torch" everywhere else.
+    ``dep_context_precision`` selects, with the same values and the same rule
+    applied to ``dep_convs`` (the stock 36-channel stack), how the
+    full-resolution refinement of cfg.PSNET_DEP_CONTEXT runs
+    (PSNet.py:218-221): ``sfm_amd.context.dep_context_refine``, which
+    upsamples the features in the dtype they arrive in, or nn.Conv2d on
+    F.interpolate + torch.cat."""
 
     def __init__(self, nlabel, mindepth=None, cfg=None, feature_fn=None, cost_dtype=torch.float32,
-                 conv_precision="auto", context_precision="auto"):
+                 conv_precision="auto", context_precision="auto", dep_context_precision="auto"):
         super().__init__(64)
         c = _default_cfg if cfg is None else cfg
         if c.get("COST_BY_COLOR", False) or c.get("COST_BY_COLOR_WITH_FEAT", False):
@@ -154,6 +162,9 @@ class PSNet(CostRegularization):
         if context_precision not in ("auto", "torch", "fp16", "bf16"):
             raise ValueError(f"unknown context precision {context_precision!r}")
         self.context_precision = context_precision
+        if dep_context_precision not in ("auto", "torch", "fp16", "bf16"):
+            raise ValueError(f"unknown dep_context precision {dep_context_precision!r}")
+        self.dep_context_precision = dep_context_precision
         self.feature_extraction = FeatureExtraction() if feature_fn is None else feature_fn
         if c.get("IND_CONTEXT", False):
             self.context_net = FeatureExtraction()
@@ -174,19 +185,28 @@ class PSNet(CostRegularization):
     def context_route(self, device=None):
         """How the context stack runs at this call: "torch", "fp16" or "bf16"
         (see ``context_precision``)."""
-        p = self.context_precision
+        return self._stack_route("context_precision", "convs", stock_layout, device)
+
+    def dep_context_route(self, device=None):
+        """How ``dep_convs`` runs at this call: "torch", "fp16" or "bf16"
+        (see ``dep_context_precision``; ``context_route``'s rule)."""
+        return self._stack_route("dep_context_precision", "dep_convs", dep_stock_layout, device)
+
+    def _stack_route(self, arg, name, layout_ok, device):
+        p = getattr(self, arg)
         if p == "torch":
             return p
         if p in ("fp16", "bf16"):
             if self.training:
-                raise RuntimeError(f"context_precision={p!r} folds BatchNorm2d and has no backward: eval mode only")
+                raise RuntimeError(f"{arg}={p!r} folds BatchNorm2d and has no backward: eval mode only")
             return p
         on_gpu = device is not None and torch.device(device).type == "cuda"
         if self.training or not on_gpu or not torch.is_autocast_enabled() or _autocast_gpu_dtype() != torch.float16:
             return "torch"
-        # the HIP route calls no module, so it is taken only where self.convs(x) would run the stock stack and
-        # nothing else (the rule psnet_depth applies to the fused sweep)
-        if self.convs._forward_hooks or self.convs._forward_pre_hooks or not stock_layout(self.convs):
+        # the HIP route calls no module, so it is taken only where self.convs(x) / self.dep_convs(x) would run
+        # the stock stack and nothing else (the rule psnet_depth applies to the fused sweep)
+        convs = getattr(self, name, None)
+        if convs is None or convs._forward_hooks or convs._forward_pre_hooks or not layout_ok(convs):
             return "torch"
         return "fp16"
 
@@ -201,6 +221,7 @@ class PSNet(CostRegularization):
         # the float32 copy of the reference features, made where something reads it: the sweep of anything but
         # float16 features on the fused route, the context stack, PSNET_DEP_CONTEXT
         ref_fea = None
+        dep_src = ref_raw           # what PSNET_DEP_CONTEXT upsamples: refimg_fea as PSNet.py:219 finds it
         costs = None
         for j, target in enumerate(targets):
             tgt_raw = self.feature_extraction(target)
@@ -230,10 +251,12 @@ class PSNet(CostRegularization):
             # the stack on libsfm_hip: the features in whatever dtype they arrive (no float32 copy), the planes
             # b-major, so the result is already the [B, L, h, w] volume the head reads
             ctx = self.context_net(ref) if c.get("IND_CONTEXT", False) else ref_raw    # PSNet.py:177-178
+            dep_src = ctx
             costss = context_refine(self.convs, ctx, costs.float(), precision=route)
         elif route == "torch":
             if c.get("IND_CONTEXT", False):
                 ref_fea = self.context_net(ref).float()        # PSNet.py:177-178 reassigns refimg_fea
+                dep_src = ref_fea
             elif ref_fea is None:
                 ref_fea = ref_raw.float()
             ctx = ref_fea
@@ -247,7 +270,15 @@ class PSNet(CostRegularization):
                                 scale=1.0 if pbd else None)
         depth = depth_head(costss.reshape(B, L, h, w).contiguous(), self.nlabel, self.mindepth, (H, W), pbd)
         if c.get("PSNET_DEP_CONTEXT", False):
-            ref_fea = ref_raw.float() if ref_fea is None else ref_fea
+            droute = self.dep_context_route(depth.device)
+            if droute in ("fp16", "bf16"):
+                # upsample, cat and the stack on libsfm_hip: the features in the dtype they arrive in, no float32
+                # copy, no full-resolution temporary but the stack's own
+                return depth, dep_context_refine(self.dep_convs, depth.detach(), dep_src, ref, precision=droute)
+            if dep_src is ref_raw:
+                ref_fea = ref_raw.float() if ref_fea is None else ref_fea
+            else:
+                ref_fea = dep_src.float()
             up = F.interpolate(ref_fea, [H, W], mode="bilinear", align_corners=True)
             feat = torch.cat((depth.detach(), up, ref.float()), dim=1)
             return depth, self.dep_convs(feat) + depth

@@ -598,6 +598,31 @@ int sfm_context_pack_f16(const float* ctx, const float* planes, int batch, int n
 int sfm_context_pack_bf16(const float* ctx, const float* planes, int batch, int nlabel, int l0, int nl, int channels,
                           int h, int w, void* out, void* stream);
 
+/* The first-stage input of the full-resolution depth refinement stack
+ * dep_convs (models/PSNet.py:218-221: up_feat = interpolate(refimg_fea,
+ * [H, W], bilinear, align_corners=True); cat((depth, up_feat, ref))) for
+ * pairs b0 .. b0+nb-1, channels-last and padded to 64 channels, the
+ * upsample fused in:
+ *   depth [dev] batch x H x W float32;
+ *   feat [dev] batch x channels x h x w, channels == 32, float32
+ *     (feat_dtype 0), bfloat16 (1) or float16 (2), read as it is;
+ *   image [dev] batch x 3 x H x W float32;
+ *   out [dev] nb x H x W x 64 float16 (round to nearest even), 16-byte
+ *     aligned: channel 0 depth, 1..32 the features at
+ *     src = dst * (in - 1) / (out - 1) (0 when out == 1), interpolated in
+ *     torch's order of operations in float64 and rounded once (a float32
+ *     evaluation is several float16 steps off where the terms cancel), 33..35
+ *     the image, 36..63 zero.  dep_convs.0.0.weight packs without a
+ *     permutation.
+ * sfm_conv2_f16 runs the stack on it (cin 64); its cout 1 stage takes depth
+ * as residual1 (PSNet.py:221 "+ depth"). */
+int sfm_dep_context_pack_f16(const float* depth, const void* feat, int feat_dtype, const float* image, int batch,
+                             int b0, int nb, int channels, int h, int w, int H, int W, void* out, void* stream);
+
+/* sfm_dep_context_pack_f16 writing bfloat16 (models/PSNet.py:218-221). */
+int sfm_dep_context_pack_bf16(const float* depth, const void* feat, int feat_dtype, const float* image, int batch,
+                              int b0, int nb, int channels, int h, int w, int H, int W, void* out, void* stream);
+
 /* Tuning knobs (process-wide; every key, its accepted values and default):
  *
  *   launch shape only -- outputs are bit-identical for every value:

@@ -262,6 +262,20 @@ int sfm_ransac5_candidate_counts(const void* workspace, size_t workspace_bytes, 
   return SFM_OK;
 }
 
+int sfm_ransac5_hypothesis_counts(const void* workspace, size_t workspace_bytes, int batch, int iters,
+                                  int32_t* nroots_host, int32_t* ncand_host) {
+  SFM_REQUIRE(workspace && nroots_host && ncand_host && batch >= 1 && batch <= SFM_MAX_BATCH && iters >= 1,
+              "invalid arguments");
+  const int bc = batch;
+  SFM_REQUIRE(workspace_bytes >= layout(nullptr, bc, 0, iters, nullptr), "workspace too small");
+  Workspace w;
+  layout((char*)workspace, bc, 0, iters, &w);
+  const size_t bytes = sizeof(int32_t) * (size_t)batch * kChains * iters;
+  SFM_HIP(hipMemcpy(nroots_host, w.nroots, bytes, hipMemcpyDeviceToHost));
+  SFM_HIP(hipMemcpy(ncand_host, w.ncand, bytes, hipMemcpyDeviceToHost));
+  return SFM_OK;
+}
+
 int sfm_ransac5_skipped_evaluations(const void* workspace, size_t workspace_bytes, int batch, int iters,
                                     unsigned long long* skipped_host) {
   SFM_REQUIRE(workspace && skipped_host && batch >= 1 && iters >= 1, "invalid arguments");

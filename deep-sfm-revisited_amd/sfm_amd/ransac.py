@@ -232,6 +232,20 @@ def candidate_counts(workspace, batch, iters):
     return [int(v) for v in out]
 
 
+def hypothesis_counts(workspace, batch, iters):
+    """Per hypothesis of the last RANSAC call that used ``workspace`` (laid out
+    for ``batch`` pairs): (nroots, ncand), two [batch, H] int32 CPU tensors -- the
+    solver's real-root count (<= 0: no valid root) and the candidates it kept
+    (synchronises)."""
+    H = hypotheses(iters)
+    nroots = torch.zeros(int(batch), H, dtype=torch.int32)
+    ncand = torch.zeros(int(batch), H, dtype=torch.int32)
+    _lib.check(_lib.load().sfm_ransac5_hypothesis_counts(_lib.ptr(workspace), workspace.numel(), int(batch),
+                                                         int(iters), _lib.ptr(nroots), _lib.ptr(ncand)),
+               "sfm_ransac5_hypothesis_counts")
+    return nroots, ncand
+
+
 def skipped_evaluations(workspace, batch, iters):
     """Evaluations the last RANSAC call that used ``workspace`` skipped by exact
     bound pruning (0 when it was off; synchronises)."""

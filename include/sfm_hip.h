@@ -166,6 +166,15 @@ int sfm_keypoints_to_points(const float* flow, int batch, int H, int W, int h_si
 int sfm_ransac5_candidate_counts(const void* workspace, size_t workspace_bytes, int batch, int iters,
                                  int32_t* counts_host);
 
+/* Per hypothesis of the last sfm_ransac5_packed / _flow call made with this
+ * workspace (laid out for `batch` pairs; the last <= SFM_MAX_BATCH chunk): the
+ * five-point solver's real-root count (<= 0: no valid root) and the candidates
+ * it kept (roots that pass cheirality; every valid root, at most 10, when
+ * cheirality == 0), copied to the host (synchronous).
+ *   nroots_host, ncand_host [host] batch x H int32, H = SFM_RANSAC_CHAINS * iters. */
+int sfm_ransac5_hypothesis_counts(const void* workspace, size_t workspace_bytes, int batch, int iters,
+                                  int32_t* nroots_host, int32_t* ncand_host);
+
 /* Evaluations the last RANSAC call with this workspace skipped by exact
  * bound pruning (tuning key score_prune; on when num_test == num_ransac_test
  * and hyp_score_out is NULL), copied to the host (synchronous).  The score

@@ -69,6 +69,8 @@ def lib():
         _lib.orc_sample_index.restype = ctypes.c_int64
         _lib.orc_philox_u32.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32]
         _lib.orc_philox_u32.restype = ctypes.c_uint32
+        _lib.orc_isolate_stats.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]
+        _lib.orc_isolate_stats.restype = None
     return _lib
 
 
@@ -108,6 +110,17 @@ def solve5(q5, qp5, cheir=True):
 def ref_solve5(q5, qp5, cheir=True):
     """Same, through the reference's own host-compiled solver."""
     return _solve5(ref(), "ref_", q5, qp5, cheir)
+
+
+ISOLATE_STATS = ("coincident", "falsi_fail", "depth_drop", "non_monotone", "slot_range", "many_nodes")
+
+
+def isolate_stats(reset=False):
+    """Branch counters of the oracle's root isolation over every solve since the
+    last reset (ransac5_oracle.cpp: g_iso_stats), as a dict."""
+    out = (ctypes.c_longlong * len(ISOLATE_STATS))()
+    lib().orc_isolate_stats(out, int(reset))
+    return dict(zip(ISOLATE_STATS, (int(v) for v in out)))
 
 
 def sample_index(seed, h, d, n):

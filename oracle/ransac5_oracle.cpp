@@ -410,24 +410,44 @@ static int count_real(int np, const SPoly* s, int* atneg, int* atpos) {
 
 struct Interval { double lo, hi; int atlo, athi, off, depth; };
 
+// Branch counters of isolate_roots, summed over every solve since the last
+// orc_isolate_stats(.., reset) (tests/solver_cases.py: which branches a scene
+// reaches, and that it stays where the GPU's split isolation is defined):
+//   [0] a multi-root bisection ended at the iteration limit and wrote several
+//       coincident roots;
+//   [1] single-root nodes where regula falsi failed (sbisect's bisection);
+//   [2] nodes dropped at kMaxDepth;
+//   [3] non-monotone sign-change counts: a split with a negative part, or a
+//       node holding fewer than one root;
+//   [4] single-root nodes or root writes whose slot is outside [0, 10);
+//   [5] solves with more than 10 single-root nodes.
+// Counts only: no result depends on them.
+enum { kStCoincident, kStFalsiFail, kStDepthDrop, kStNonMonotone, kStSlotRange, kStManyNodes, kStCount };
+static long long g_iso_stats[kStCount];
+static inline void iso_count(int k) { __atomic_fetch_add(&g_iso_stats[k], 1LL, __ATOMIC_RELAXED); }
+
 // sbisect<depth> (sturm.cu:450-555) with an explicit work stack.  Root slots
 // outside [0,10) (possible only for a numerically non-monotone sequence) are
 // not written — the reference would write out of bounds there.
 static void isolate_roots(int np, const SPoly* s, double lo, double hi, int atlo, int athi, double* roots) {
   Interval stk[64];
-  int sp = 0;
+  int sp = 0, single = 0;
   stk[sp++] = Interval{lo, hi, atlo, athi, 0, 0};
   while (sp > 0) {
     Interval iv = stk[--sp];
-    if (iv.depth >= kMaxDepth) continue;
+    if (iv.depth >= kMaxDepth) { iso_count(kStDepthDrop); continue; }
     double mn = iv.lo, mx = iv.hi, mid = 0.0;
     int n = iv.atlo - iv.athi;
+    if (n < 1) iso_count(kStNonMonotone);
     if (n == 1) {
+      if (++single == 11) iso_count(kStManyNodes);
+      if (iv.off < 0 || iv.off >= 10) iso_count(kStSlotRange);
       double v;
       if (regula_falsi_any(s[0].ord, s[0].c, mn, mx, &v)) {
         if (iv.off >= 0 && iv.off < 10) roots[iv.off] = v;
         continue;
       }
+      iso_count(kStFalsiFail);
       int it;
       bool done = false;
       for (it = 0; it < kMaxIt; ++it) {
@@ -449,6 +469,7 @@ static void isolate_roots(int np, const SPoly* s, double lo, double hi, int atlo
       n1 = iv.atlo - atmid;
       int n2 = atmid - iv.athi;
       if (n1 != 0 && n2 != 0) {
+        if (n1 < 0 || n2 < 0) iso_count(kStNonMonotone);
         if (sp + 2 <= 64) {
           stk[sp++] = Interval{mid, mx, atmid, iv.athi, iv.off + n1, iv.depth + 1};
           stk[sp++] = Interval{mn, mid, iv.atlo, atmid, iv.off, iv.depth + 1};
@@ -457,11 +478,14 @@ static void isolate_roots(int np, const SPoly* s, double lo, double hi, int atlo
       }
       if (n1 == 0) mn = mid; else mx = mid;
     }
-    if (it == kMaxIt)
+    if (it == kMaxIt) {
+      if (iv.atlo - iv.athi >= 2) iso_count(kStCoincident);
       for (int r = iv.athi; r < iv.atlo; ++r) {
         int slot = iv.off + r - iv.athi;
         if (slot >= 0 && slot < 10) roots[slot] = mid;
+        else iso_count(kStSlotRange);
       }
+    }
   }
 }
 
@@ -760,6 +784,14 @@ using namespace orc;
 extern "C" {
 
 int orc_version(void) { return 1; }
+
+// isolate_roots' branch counters (kStCount = 6 values) since the last reset.
+void orc_isolate_stats(long long* out, int reset) {
+  for (int k = 0; k < kStCount; ++k) {
+    if (out) out[k] = __atomic_load_n(&g_iso_stats[k], __ATOMIC_RELAXED);
+    if (reset) __atomic_store_n(&g_iso_stats[k], 0LL, __ATOMIC_RELAXED);
+  }
+}
 
 uint32_t orc_philox_u32(uint64_t seed, uint32_t h, uint32_t d) { return draw_u32(seed, h, d); }
 

@@ -1,6 +1,6 @@
 // float32 <-> 16-bit activation conversions of the regularisation stack, shared
 // by its kernels (regularize.hip: Act<F16>, k_to_channels_last*) and by the
-// plane sweep that writes the stack's channels-last input itself (sweep.hip:
+// plane sweep that writes the stack's channels-last input itself (sweep_cl.hip:
 // k_sweep_cl), so that both round a float32 cost value with the same function.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -271,7 +271,7 @@ __device__ __forceinline__ void rider_store(const R& rj, unsigned p, int lane, c
   const unsigned step = rj.P * esz;
   unsigned voff = (n0 * rj.P + 256u * j + 4u * (unsigned)lane) * esz;
   if (!d.live) return;
-  // (a literal-0 soffset: the 128-bit stores' data hazard, sweep.hip)
+  // (a literal-0 soffset: the 128-bit stores' data hazard, sweep_tile.hip)
   if constexpr (R::fmt == 1) {
     typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
     const u32x4_t v = {__float_as_uint(d.a.x), __float_as_uint(d.a.y), __float_as_uint(d.b.x), __float_as_uint(d.b.y)};

@@ -1,5 +1,6 @@
 // Projection / sampling helpers shared by the plane-sweep kernels
-// (sweep.hip: cost volume, inverse warp; depth.hip: correlation cost).
+// (sweep.hip and the sweep_*.hip kernel forms: cost volume, inverse warp;
+// depth.hip: correlation cost).
 //
 // Arithmetic follows the reference's float32 expression order:
 //   cam = (Kinv . (x, y, 1)) * d              pixel2cam (inverse_warp.py:27-41)

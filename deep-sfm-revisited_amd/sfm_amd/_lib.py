@@ -149,6 +149,7 @@ _SIGS = [
     ("sfm_tune_get", ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]),
     ("sfm_tune_key", ctypes.c_char_p, [ctypes.c_int]),
     ("sfm_last_scorer", ctypes.c_char_p, []),
+    ("sfm_last_sweep", ctypes.c_char_p, []),
     ("sfm_profile_enable", ctypes.c_int, [ctypes.c_int]),
     ("sfm_profile_select", ctypes.c_int, [ctypes.c_char_p]),
     ("sfm_profile_reset", ctypes.c_int, []),
@@ -267,3 +268,8 @@ def tune_restore(snap):
 def last_scorer():
     """The score kernel the last RANSAC / score call dispatched (sfm_last_scorer)."""
     return load().sfm_last_scorer().decode()
+
+
+def last_sweep():
+    """The kernel form the last plane-sweep call on this thread launched (sfm_last_sweep)."""
+    return load().sfm_last_sweep().decode()

@@ -746,6 +746,21 @@ const char* sfm_tune_key(int index);
  * followed by "+prune" when k_score_mf2 ran with count-bound pruning (two
  * launches and k_mf2_lead / k_mf2_keep between them).  A dispatch check for tests. */
 const char* sfm_last_scorer(void);
+/* The kernel form the most recent plane-sweep call of this thread launched
+ * ("" before any), taken from the call's launch plan.  A dispatch check for
+ * tests.  The planar entries (sfm_plane_sweep, _ex, _warped, _psnet,
+ * _psnet_warped_half):
+ *   "k_sweep_tile+wide"  k_sweep_tile whose interior windows use 16-byte stores (the default)
+ *   "k_sweep_tile"       k_sweep_tile with 4-byte stores (odd slab, unaligned
+ *                        output, sweep_share, sweep_store_px = 0, sweep_buffer = 0)
+ *   "k_sweep_flat"       sweep_flat = 1, and sweep_flat = 3 whose band does not fit
+ *   "k_sweep_band"       sweep_flat = 3
+ *   "k_sweep+vec"        the per-row form with 16-byte row stores (sweep_flat = 0,
+ *                        or a shape outside the other forms' range)
+ *   "k_sweep"            the per-row form with element stores
+ * sfm_plane_sweep_cl, _cl_f16: "k_sweep_cl" (the fast path) or "k_sweep_cl_any";
+ * sfm_plane_sweep_ref_planes: "k_ref_planes" or "k_ref_planes_generic". */
+const char* sfm_last_sweep(void);
 
 /* ------------------------------------------------------------------------
  * Per-kernel timing (HIP events recorded around every launch on the

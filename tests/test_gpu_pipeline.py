@@ -68,6 +68,8 @@ def test_ref_planes_alone_write_only_the_reference_rows(cuda):
     ref, _ = synth.features(B, C, h, w, seed=5, device=cuda)
     out = torch.full((B, 2 * C, L, h, w), 7.0, device=cuda)
     sweep.plane_sweep_ref_half(ref, L, out)
+    from sfm_amd import _lib
+    assert _lib.last_sweep() == "k_ref_planes_generic"      # L * h * w is no multiple of 64
     torch.cuda.synchronize()
     assert torch.equal(out[:, :C], ref.unsqueeze(2).expand(B, C, L, h, w))
     assert bool((out[:, C:] == 7.0).all())

@@ -85,6 +85,9 @@ def test_bit_equal_to_sweep_then_transpose(cuda, case, dtype):
     from sfm_amd.sweep import plane_sweep_cost_channels_last
     h, w, L, C, B = case
     got = plane_sweep_cost_channels_last(*_args(case, cuda), dtype=dtype)
+    from sfm_amd import _lib
+    # the fast path takes whole 16-byte chunks per record half: C % 4 (float32) or C % 8 (16-bit)
+    assert _lib.last_sweep() == ("k_sweep_cl" if C % (4 if dtype == torch.float32 else 8) == 0 else "k_sweep_cl_any")
     assert tuple(got.shape) == (B, L, h, w, 2 * C) and got.dtype == dtype and got.is_contiguous()
     assert _bits_equal(got, _two_step(case, cuda, dtype))
 
@@ -98,6 +101,8 @@ def test_element_wise_kernel_with_a_padded_quad(cuda, dtype):
     from sfm_amd.sweep import plane_sweep_cost_channels_last
     case = (9, 13, 3, 6, 2)
     got = plane_sweep_cost_channels_last(*_args(case, cuda), dtype=dtype)
+    from sfm_amd import _lib
+    assert _lib.last_sweep() == "k_sweep_cl_any"
     planar = _planar_cost(case, cuda)
     assert bool((planar[:, 6:] != 0).any())
     if dtype == torch.float32:

@@ -20,6 +20,9 @@ from oracle import sweep as S
 pytestmark = pytest.mark.gpu
 
 RTOL, FLOOR = 1e-4, 1.0    # the tolerance of test_gpu_sweep.py: 1e-4 * max(|b|, feature RMS)
+# sweep_flat -> what sfm_last_sweep() may say (every band of these tests fits the LDS)
+FORMS = {0: ("k_sweep", "k_sweep+vec"), 1: ("k_sweep_flat",), 2: ("k_sweep_tile", "k_sweep_tile+wide"),
+         3: ("k_sweep_band",)}
 
 
 @pytest.mark.parametrize("B,C,L,h,w,dtype,offset", [
@@ -62,6 +65,7 @@ def test_aligned_slab_kernels_match_per_row(cuda, B, C, L, h, w, dtype, offset):
             buf = torch.full((n + offset,), float("nan"), dtype=dtype, device=cuda)
             out = buf[offset:].view(B, 2 * C, L, h, w)
             plane_sweep_cost(*args, dtype=dtype, out=out)
+            assert _lib.last_sweep() in FORMS[flat], (flat, group, nj, _lib.last_sweep())
             outs[(flat, group, nj) if _lib.tune_get("sweep_buffer") else (flat, group, -nj)] = out.float().cpu()
     finally:
         _lib.tune("sweep_flat", 2)
@@ -118,6 +122,7 @@ def test_band_kernel_full_size_kitti(cuda, dtype, run, rows):
         _lib.tune("sweep_run", run)
         _lib.tune("sweep_band_rows", rows)
         got = plane_sweep_cost(*args, dtype=dtype)
+        assert _lib.last_sweep() == "k_sweep_band"
     finally:
         _lib.tune("sweep_flat", 2)
         _lib.tune("sweep_run", 16)
@@ -156,6 +161,8 @@ def test_shared_taps_equal_gathered(cuda, dtype, B, C, L, hw, tscale, by_depth):
             _lib.tune("sweep_share", share)
             _lib.tune("sweep_store_nt", nt)
             outs.append(plane_sweep_cost(*args, dtype=dtype, predict_by_depth=by_depth))
+            if share:
+                assert _lib.last_sweep() == "k_sweep_tile"      # shared taps exclude the wide stores
     finally:
         _lib.tune("sweep_share", old[0])
         _lib.tune("sweep_store_nt", old[1])

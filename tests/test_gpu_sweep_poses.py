@@ -150,6 +150,11 @@ def _run_form(tuning, snap, args, dtype, shape):
             _lib.tune(k, v)
     out = torch.full(shape, float("nan"), dtype=dtype, device=args[0].device)
     plane_sweep_cost(*args, dtype=dtype, out=out)
+    if tuning is not None:      # the form the keys select is the one that ran
+        want = {0: "k_sweep", 1: "k_sweep_flat", 2: "k_sweep_tile", 3: "k_sweep_band"}[_lib.tune_get("sweep_flat")]
+        assert _lib.last_sweep().split("+")[0] == want, (tuning, _lib.last_sweep())
+        if tuning.get("sweep_share") or tuning.get("sweep_buffer") == 0:
+            assert _lib.last_sweep() == "k_sweep_tile", (tuning, _lib.last_sweep())
     return out
 
 

@@ -141,6 +141,15 @@ _SIGS = [
     ("sfm_dep_context_pack_bf16", ctypes.c_int,
      [_c_dp, _c_dp, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
       ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp]),
+    ("sfm_conv2x_f16", ctypes.c_int,
+     [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+      ctypes.c_int, _c_dp, _c_dp, ctypes.c_int, _c_dp, _c_dp, _c_dp]),
+    ("sfm_image_pack_f16", ctypes.c_int, [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp]),
+    ("sfm_avgpool_f16", ctypes.c_int,
+     [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp]),
+    ("sfm_spp_pack_f16", ctypes.c_int,
+     [_c_dp, _c_dp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+      ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp]),
     ("sfm_score_essentials_workspace_bytes", ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     ("sfm_score_essentials", ctypes.c_int,
      [_c_dp, ctypes.c_int64, _i64p, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.c_double, _c_dp, _c_dp,

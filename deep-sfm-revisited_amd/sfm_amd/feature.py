@@ -1,0 +1,360 @@
+"""PSNet's feature CNN on the gfx950 matrix cores.
+
+The reference extracts 32-channel quarter-resolution features from every
+image with PSMNet's SPP network (models/submodule.py:108-184
+``feature_extraction``; ``sfm_amd.psnet.FeatureExtraction`` here): a stride-2
+stem, four stages of residual blocks, four average-pool pyramid branches
+upsampled back, and a 320 -> 128 -> 32 fusion.
+
+``feature_extract`` runs it on libsfm_hip: one ``sfm_image_pack_f16``, every
+Conv2d as an ``sfm_conv2x_f16`` launch (float16 channels-last activations and
+weights, fp32 accumulation, BatchNorm2d folded in eval mode, the ReLU and the
+block's "+ x" fused into the epilogue, ``downsample`` as a 1 x 1 launch feeding
+that residual), four ``sfm_avgpool_f16``, one ``sfm_spp_pack_f16`` (the bilinear
+upsamples and the cat) -- the precision torch computes this network at under
+``cfg.MIXED_PREC`` autocast (SFMnet.py:164).  There is no PyTorch fallback:
+without libsfm_hip.so or a GPU the call raises.
+"""
+import ctypes
+import weakref
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+
+MIN_MAP = 32            # AvgPool2d(32) needs a 32 x 32 quarter-resolution map
+
+
+class FeatureLayoutError(RuntimeError):
+    """The module is not the stock FeatureExtraction graph ``feature_extract`` runs."""
+
+
+def _half(n):
+    return (n - 1) // 2 + 1
+
+
+def feature_hw(image_hw):
+    """Quarter-resolution map size of the CNN for an image (two stride-2 convs)."""
+    return _half(_half(image_hw[0])), _half(_half(image_hw[1]))
+
+
+def _conv_bn(seq, cin, cout, k, stride, dilation, what, bn=True):
+    """(conv, bn) of a stock conv-BN pair, or FeatureLayoutError naming what differs."""
+    mods = list(seq) if isinstance(seq, nn.Sequential) else [seq]
+    if len(mods) != (2 if bn else 1) or not isinstance(mods[0], nn.Conv2d) or \
+            (bn and not isinstance(mods[1], nn.BatchNorm2d)):
+        raise FeatureLayoutError(f"{what}: expected Conv2d{' + BatchNorm2d' if bn else ''}")
+    conv = mods[0]
+    pad = dilation if k == 3 else 0
+    if (conv.in_channels, conv.out_channels) != (cin, cout):
+        raise FeatureLayoutError(f"{what}: {conv.in_channels} -> {conv.out_channels} channels, expected {cin} -> {cout}")
+    if tuple(conv.kernel_size) != (k, k):
+        raise FeatureLayoutError(f"{what}: kernel size {tuple(conv.kernel_size)}, expected {k} x {k}")
+    if tuple(conv.stride) != (stride, stride):
+        raise FeatureLayoutError(f"{what}: stride {tuple(conv.stride)}, expected {stride}")
+    if tuple(conv.dilation) != (dilation, dilation):
+        raise FeatureLayoutError(f"{what}: dilation {tuple(conv.dilation)}, expected {dilation}")
+    if tuple(conv.padding) != (pad, pad) or conv.padding_mode != "zeros":
+        raise FeatureLayoutError(f"{what}: padding {conv.padding}, expected {pad} (zeros)")
+    if conv.groups != 1:
+        raise FeatureLayoutError(f"{what}: grouped convolutions are not built")
+    if conv.bias is not None:
+        raise FeatureLayoutError(f"{what}: a Conv2d bias is not built (convbn has none)")
+    if not bn:
+        return conv, None
+    b = mods[1]
+    if b.num_features != cout or not b.track_running_stats or b.running_mean is None or b.running_var is None:
+        raise FeatureLayoutError(f"{what}: BatchNorm2d without running statistics cannot be folded")
+    return conv, b
+
+
+def _plan(module):
+    """The CNN as (conv, bn, relu) stages in execution order, or
+    FeatureLayoutError: {"first": [3], "layers": [[(conv1, conv2, downsample
+    or None)] x blocks] x 4, "branches": [(pool, stage)] x 4 (branch1..4),
+    "last": [2]}."""
+    from .psnet import FeatureExtraction, _Residual
+    if type(module) is not FeatureExtraction:
+        raise FeatureLayoutError(f"{type(module).__name__} is not sfm_amd.psnet.FeatureExtraction")
+    want = ["firstconv"] + [s[0] for s in module.STAGES] + [f"branch{i + 1}" for i in range(4)] + ["lastconv"]
+    names = [n for n, _ in module.named_children()]
+    if names != want:
+        raise FeatureLayoutError(f"children {names}, expected {want}")
+    if tuple(module.STAGES) != FeatureExtraction.STAGES or tuple(module.POOLS) != FeatureExtraction.POOLS:
+        raise FeatureLayoutError("STAGES / POOLS differ from the stock plan")
+    fc = module.firstconv
+    if not isinstance(fc, nn.Sequential) or len(fc) != 6 or not all(isinstance(fc[i], nn.ReLU) for i in (1, 3, 5)):
+        raise FeatureLayoutError("firstconv: expected three conv-BN + ReLU stages")
+    first = [_conv_bn(fc[0], 3, 32, 3, 2, 1, "firstconv.0") + (True,),
+             _conv_bn(fc[2], 32, 32, 3, 1, 1, "firstconv.2") + (True,),
+             _conv_bn(fc[4], 32, 32, 3, 1, 1, "firstconv.4") + (True,)]
+    layers, cin = [], 32
+    for name, ch, blocks, stride, dil in FeatureExtraction.STAGES:
+        seq = getattr(module, name)
+        if not isinstance(seq, nn.Sequential) or len(seq) != blocks:
+            raise FeatureLayoutError(f"{name}: expected {blocks} residual blocks")
+        blks = []
+        for i, blk in enumerate(seq):
+            what = f"{name}.{i}"
+            if type(blk) is not _Residual:
+                raise FeatureLayoutError(f"{what}: {type(blk).__name__} is not the stock residual block")
+            s = stride if i == 0 else 1
+            c1 = blk.conv1
+            if not isinstance(c1, nn.Sequential) or len(c1) != 2 or not isinstance(c1[1], nn.ReLU):
+                raise FeatureLayoutError(f"{what}.conv1: expected conv-BN + ReLU")
+            a = _conv_bn(c1[0], cin, ch, 3, s, dil, what + ".conv1") + (True,)
+            b = _conv_bn(blk.conv2, ch, ch, 3, 1, dil, what + ".conv2") + (False,)
+            need_ds = s != 1 or cin != ch
+            if (blk.downsample is not None) != need_ds:
+                raise FeatureLayoutError(f"{what}: downsample {'missing' if need_ds else 'unexpected'}")
+            ds = _conv_bn(blk.downsample, cin, ch, 1, s, 1, what + ".downsample") + (False,) if need_ds else None
+            blks.append((a, b, ds))
+            cin = ch
+        layers.append(blks)
+    branches = []
+    for i, p in enumerate(FeatureExtraction.POOLS):
+        br = getattr(module, f"branch{i + 1}")
+        what = f"branch{i + 1}"
+        if not isinstance(br, nn.Sequential) or len(br) != 3 or not isinstance(br[0], nn.AvgPool2d) or \
+                not isinstance(br[2], nn.ReLU):
+            raise FeatureLayoutError(f"{what}: expected AvgPool2d + conv-BN + ReLU")
+        pool = br[0]
+        ks = pool.kernel_size if isinstance(pool.kernel_size, tuple) else (pool.kernel_size,) * 2
+        st = pool.stride if isinstance(pool.stride, tuple) else (pool.stride,) * 2
+        pd = pool.padding if isinstance(pool.padding, tuple) else (pool.padding,) * 2
+        if tuple(ks) != (p, p) or tuple(st) != (p, p) or tuple(pd) != (0, 0) or pool.ceil_mode or \
+                pool.divisor_override is not None:
+            raise FeatureLayoutError(f"{what}: AvgPool2d {ks} stride {st}, expected {p} x {p} stride {p}")
+        branches.append((p, _conv_bn(br[1], 128, 32, 1, 1, 1, what + ".1") + (True,)))
+    lc = module.lastconv
+    if not isinstance(lc, nn.Sequential) or len(lc) != 3 or not isinstance(lc[1], nn.ReLU):
+        raise FeatureLayoutError("lastconv: expected conv-BN + ReLU + Conv2d")
+    last = [_conv_bn(lc[0], 320, 128, 3, 1, 1, "lastconv.0") + (True,),
+            _conv_bn(lc[2], 128, 32, 1, 1, 1, "lastconv.2", bn=False) + (False,)]
+    return dict(first=first, layers=layers, branches=branches, last=last)
+
+
+def feature_layout_ok(module):
+    """Whether ``module`` is exactly the stock FeatureExtraction graph: its
+    named children, every Conv2d's kernel, stride, padding, dilation, groups
+    and lack of bias, running statistics on every BatchNorm2d, the pool sizes
+    and the channel plan.  Anything else (another class, a callable) is False."""
+    try:
+        _plan(module)
+    except FeatureLayoutError:
+        return False
+    return True
+
+
+def _pad32(n):
+    return (n + 31) // 32 * 32
+
+
+def _pack_stage(stage, device):
+    conv, bn, relu = stage
+    w = conv.weight.detach().float().cpu()                         # [cout, cin, k, k]
+    cout, cin, k = w.shape[0], w.shape[1], w.shape[2]
+    cout_pad, cin_pad = _pad32(cout), _pad32(cin)
+    wp = torch.zeros(k * k, cout_pad, cin_pad, dtype=torch.float32)
+    wp[:, :cout, :cin] = w.permute(2, 3, 0, 1).reshape(k * k, cout, cin)
+    sc, bi = torch.ones(cout_pad), torch.zeros(cout_pad)
+    if bn is not None:
+        g = torch.ones(cout) if bn.weight is None else bn.weight.detach().float().cpu()
+        b = torch.zeros(cout) if bn.bias is None else bn.bias.detach().float().cpu()
+        scale = g / torch.sqrt(bn.running_var.detach().float().cpu() + bn.eps)
+        sc[:cout] = scale
+        bi[:cout] = b - bn.running_mean.detach().float().cpu() * scale
+    return dict(w=wp.to(device=device, dtype=torch.float16).contiguous(), scale=sc.to(device), bias=bi.to(device),
+                cin=cin, cin_pad=cin_pad, cout=cout, cout_pad=cout_pad, ksize=k, stride=int(conv.stride[0]),
+                dilation=int(conv.dilation[0]), relu=relu)
+
+
+_PACKED = weakref.WeakKeyDictionary()      # module -> (key, packed)
+
+
+def pack_feature_extraction(module, device):
+    """Packed float16 weights [k^2][cout_pad][cin_pad] (tap = kh*k + kw; rows
+    beyond cout and columns beyond cin zero) and the folded fp32 scale / bias
+    [cout_pad] of every Conv2d of the stock CNN, in ``_plan``'s structure.
+    BatchNorm2d folds with its running statistics (eval mode), as
+    ``pack_context_stack`` folds it.  Cached until a parameter or buffer
+    changes."""
+    plan = _plan(module)
+    key = (str(device),) + tuple((t.data_ptr(), t._version) for t in list(module.parameters()) + list(module.buffers()))
+    hit = _PACKED.get(module)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    with torch.no_grad():
+        packed = dict(
+            first=[_pack_stage(s, device) for s in plan["first"]],
+            layers=[[tuple(None if s is None else _pack_stage(s, device) for s in blk) for blk in blks]
+                    for blks in plan["layers"]],
+            branches=[(p, _pack_stage(s, device)) for p, s in plan["branches"]],
+            last=[_pack_stage(s, device) for s in plan["last"]])
+    _PACKED[module] = (key, packed)
+    return packed
+
+
+# --- single launches ------------------------------------------------------------------
+def _check_act(t, name, channels=None):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float16 and t.is_contiguous() and t.dim() == 4):
+        raise RuntimeError(f"{name} must be a contiguous float16 device tensor [images, h, w, channels]")
+    if channels is not None and t.shape[3] != channels:
+        raise RuntimeError(f"{name} must have {channels} channels")
+
+
+def conv2x_f16(x, weights, scale, bias, ksize=3, stride=1, dilation=1, relu=True, residual=None):
+    """One fused layer (sfm_conv2x_f16): x [images, h, w, cin] float16,
+    weights [ksize^2, cout, cin] float16, scale / bias [cout] fp32, residual
+    [images, hout, wout, cout] float16 or None -> [images, hout, wout, cout]
+    float16."""
+    _check_act(x, "x")
+    n, h, w, cin = x.shape
+    if not (isinstance(weights, torch.Tensor) and weights.is_cuda and weights.dtype == torch.float16 and
+            weights.is_contiguous() and weights.dim() == 3 and weights.shape[0] == ksize * ksize and
+            weights.shape[2] == cin):
+        raise RuntimeError(f"weights must be a contiguous float16 device tensor [{ksize * ksize}, cout, {cin}]")
+    cout = weights.shape[1]
+    scale = scale.to(device=x.device, dtype=torch.float32).contiguous()
+    bias = bias.to(device=x.device, dtype=torch.float32).contiguous()
+    if scale.numel() != cout or bias.numel() != cout:
+        raise RuntimeError(f"scale and bias must have {cout} entries")
+    if stride not in (1, 2):
+        raise RuntimeError("stride must be 1 or 2")
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    if residual is not None:
+        _check_act(residual, "residual", cout)
+        if tuple(residual.shape) != (n, ho, wo, cout):
+            raise RuntimeError(f"residual must be [{n}, {ho}, {wo}, {cout}]")
+    out = torch.empty((n, ho, wo, cout), dtype=torch.float16, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().sfm_conv2x_f16(_lib.ptr(x), n, cin, h, w, _lib.ptr(weights), cout, int(ksize), int(stride),
+                                        int(dilation), _lib.ptr(scale), _lib.ptr(bias), 1 if relu else 0,
+                                        _lib.ptr(residual), _lib.ptr(out), _lib.stream_ptr(x.device))
+        _lib.check(rc, "sfm_conv2x_f16")
+    return out
+
+
+def image_pack_f16(image):
+    """[B, 3, H, W] float32 -> [B, H, W, 32] float16, channels 3..31 zero (sfm_image_pack_f16)."""
+    if not (isinstance(image, torch.Tensor) and image.is_cuda and image.dtype == torch.float32 and
+            image.is_contiguous() and image.dim() == 4 and image.shape[1] == 3):
+        raise RuntimeError("image must be a contiguous float32 device tensor [B, 3, H, W]")
+    B, _, H, W = image.shape
+    out = torch.empty((B, H, W, 32), dtype=torch.float16, device=image.device)
+    with torch.cuda.device(image.device):
+        _lib.check(_lib.load().sfm_image_pack_f16(_lib.ptr(image), B, H, W, _lib.ptr(out),
+                                                  _lib.stream_ptr(image.device)), "sfm_image_pack_f16")
+    return out
+
+
+def avgpool_f16(x, pool):
+    """AvgPool2d(pool, stride pool) of [images, h, w, C] float16 (sfm_avgpool_f16)."""
+    _check_act(x, "x")
+    n, h, w, C = x.shape
+    if h < pool or w < pool:
+        raise RuntimeError(f"a {h} x {w} map holds no {pool} x {pool} window")
+    out = torch.empty((n, h // pool, w // pool, C), dtype=torch.float16, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().sfm_avgpool_f16(_lib.ptr(x), n, h, w, C, int(pool), _lib.ptr(out),
+                                               _lib.stream_ptr(x.device)), "sfm_avgpool_f16")
+    return out
+
+
+def spp_pack_f16(raw, skip, branches):
+    """cat(raw, skip, up(branches[0]), .. up(branches[3])) channels-last
+    (sfm_spp_pack_f16): raw [images, h, w, 64], skip [images, h, w, 128],
+    branches four [images, hi, wi, 32] maps in cat order (branch4 .. branch1)
+    -> [images, h, w, 320] float16."""
+    _check_act(raw, "raw", 64)
+    _check_act(skip, "skip", 128)
+    n, h, w, _ = raw.shape
+    if tuple(skip.shape[:3]) != (n, h, w) or len(branches) != 4:
+        raise RuntimeError("skip must match raw, with four branch maps")
+    for b in branches:
+        _check_act(b, "branch", 32)
+        if b.shape[0] != n:
+            raise RuntimeError("every branch map must hold the same images")
+    out = torch.empty((n, h, w, 320), dtype=torch.float16, device=raw.device)
+    ptrs = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in branches])
+    bh = (ctypes.c_int * 4)(*[b.shape[1] for b in branches])
+    bw = (ctypes.c_int * 4)(*[b.shape[2] for b in branches])
+    with torch.cuda.device(raw.device):
+        _lib.check(_lib.load().sfm_spp_pack_f16(_lib.ptr(raw), _lib.ptr(skip), ptrs, bh, bw, n, h, w, _lib.ptr(out),
+                                                _lib.stream_ptr(raw.device)), "sfm_spp_pack_f16")
+    return out
+
+
+# --- the whole CNN ----------------------------------------------------------------------
+def scratch_bytes_per_image(H, W):
+    """Upper bound on the float16 activations alive at once for one image: the
+    packed image next to the stem's first output; three half-resolution
+    32-channel maps (a block's input, middle and output); at quarter resolution
+    raw, three 128-channel maps, the four branch maps (at most 1/16 of the map
+    each) and lastconv's 320-channel input."""
+    H2, W2 = _half(H), _half(W)
+    h, w = _half(H2), _half(W2)
+    return 2 * max(H * W * 32 + H2 * W2 * 32, 3 * H2 * W2 * 32, h * w * (64 + 3 * 128 + 320 + 8))
+
+
+def images_per_chunk(batch, H, W, max_scratch_bytes):
+    """The most images whose activations fit ``max_scratch_bytes``; at least one, at most batch."""
+    return max(1, min(int(batch), int(max_scratch_bytes) // scratch_bytes_per_image(H, W)))
+
+
+def _layer(x, lay, residual=None):
+    return conv2x_f16(x, lay["w"], lay["scale"], lay["bias"], lay["ksize"], lay["stride"], lay["dilation"],
+                      relu=lay["relu"], residual=residual)
+
+
+def _run(packed, image):
+    x = image_pack_f16(image)
+    for lay in packed["first"]:
+        x = _layer(x, lay)
+    raw = None
+    for i, blks in enumerate(packed["layers"]):
+        for c1, c2, ds in blks:
+            x = _layer(_layer(x, c1), c2, residual=x if ds is None else _layer(x, ds))
+        if i == 1:
+            raw = x
+    pyr = [_layer(avgpool_f16(x, p), lay) for p, lay in packed["branches"]]        # branch1..4
+    y = spp_pack_f16(raw, x, pyr[::-1])
+    for lay in packed["last"]:
+        y = _layer(y, lay)
+    return y
+
+
+def feature_extract(module, image, max_scratch_bytes=1 << 30):
+    """``module(image)`` for the stock FeatureExtraction in eval mode
+    (submodule.py:161-184): image [B, 3, H, W] (any float dtype) -> [B, 32,
+    h, w] float16, contiguous.  The images go through in chunks of
+    ``images_per_chunk``; every image is computed on its own, so the result
+    depends neither on the chunking nor on the batch.  No PyTorch fallback:
+    CPU tensors raise; so does a quarter-resolution map under 32 x 32 (torch's
+    AvgPool2d(32) fails there too)."""
+    if not (isinstance(image, torch.Tensor) and image.is_cuda):
+        raise RuntimeError("feature_extract needs a device tensor (HIP path, no CPU fallback): image")
+    if image.dim() != 4 or image.shape[1] != 3 or not image.is_floating_point():
+        raise RuntimeError("image must be [B, 3, H, W] floating point")
+    if not feature_layout_ok(module):
+        _plan(module)           # raises the named reason
+    B, _, H, W = image.shape
+    h, w = feature_hw((H, W))
+    if h < MIN_MAP or w < MIN_MAP:
+        raise RuntimeError(f"the quarter-resolution map {h} x {w} is under {MIN_MAP} x {MIN_MAP}: branch1's "
+                           f"AvgPool2d({MIN_MAP}) has no window")
+    dev = image.device
+    packed = pack_feature_extraction(module, dev)
+    image = image.detach().float().contiguous()
+    nb_max = images_per_chunk(B, H, W, max_scratch_bytes)
+    if nb_max >= B:
+        out = _run(packed, image)
+    else:
+        out = torch.empty((B, h, w, 32), dtype=torch.float16, device=dev)
+        for b0 in range(0, B, nb_max):
+            part = image[b0:b0 + nb_max]
+            if part.data_ptr() % 16:
+                part = part.clone()
+            out[b0:b0 + nb_max].copy_(_run(packed, part))
+    return out.permute(0, 3, 1, 2).contiguous()

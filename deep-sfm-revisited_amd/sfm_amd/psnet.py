@@ -5,8 +5,11 @@ The reference builds ``PSNet(nlabel, min_depth)`` inside ``SFMnet.__init__``
 PSNet's module names and constructor, so a PSNet state_dict loads unchanged,
 and runs its forward with the hot path on libsfm_hip:
 
-  feature_extraction  2-D CNN at 1/4 resolution, 32 channels         torch (MIOpen)
-                      (PSMNet SPP layout, models/submodule.py:108-184)
+  feature_extraction  2-D CNN at 1/4 resolution, 32 channels         sfm_image_pack_f16, sfm_conv2x_f16 (HIP MFMA),
+                      (PSMNet SPP layout, models/submodule.py:108-184)  sfm_avgpool_f16, sfm_spp_pack_f16 under float16
+                      and context_net (IND_CONTEXT)                    autocast in eval mode (``feature_precision``:
+                                                                       2.25 ms against 7.04 per KITTI pair,
+                                                                       profiles/feature_ab.txt); else torch (MIOpen)
   plane sweep         cost [B, 64, L, h, w] (PSNet.py:130-158)        sfm_plane_sweep (HIP); by default written
                       channels-last for the next stage                 sfm_plane_sweep_cl (HIP); float16 features
                       (cfg.MIXED_PREC) read as they come               sfm_plane_sweep_cl_f16 (HIP)
@@ -18,20 +21,27 @@ and runs its forward with the hot path on libsfm_hip:
                       sfm_dep_context_pack_* (HIP), the stack      sfm_conv2_* (HIP MFMA) under float16 autocast
                       in eval mode (``dep_context_precision``); else   torch (MIOpen)
 
-The 2-D CNNs are outside the measured path (feature CNN and
-context networks are out of scope); they are plain torch modules here so the
-estimator is complete and a reference checkpoint's weights apply.  The
+The 2-D CNNs are outside bench.py's measured path (feature
+CNN and context networks are out of scope); they are plain torch modules here,
+so the estimator is complete and a reference checkpoint's weights apply, and
+the HIP routes read those modules' parameters.  The
 ``COST_BY_COLOR`` ablations (PSNet.py:75-78, 181-188) are not built.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import feature as _feature
 from .config import cfg as _default_cfg
 from .context import context_refine, dep_context_refine, dep_stock_layout, stock_layout
 from .depth import depth_head
 from .regularize import CostRegularization, f16_features, fused_channels_last, sweep_regularize_fused
 from .sweep import plane_sweep_cost, quarter_intrinsics
+
+
+# Whether feature_precision="auto" may resolve to "fp16": the same-process A/B of scripts/feature_ab.py decides it
+# (profiles/feature_ab.txt: HIP 2.246 ms, torch float16 autocast 7.043 ms per KITTI pair of images)
+FEATURE_AUTO_HIP = True
 
 
 def _autocast_gpu_dtype():
@@ -142,10 +152,18 @@ class PSNet(CostRegularization):
     full-resolution refinement of cfg.PSNET_DEP_CONTEXT runs
     (PSNet.py:218-221): ``sfm_amd.context.dep_context_refine``, which
     upsamples the features in the dtype they arrive in, or nn.Conv2d on
-    F.interpolate + torch.cat."""
+    F.interpolate + torch.cat.  ``feature_precision`` ("auto", "torch" or
+    "fp16") selects by the same rule how ``feature_extraction`` and, under
+    cfg.IND_CONTEXT, ``context_net`` run: ``sfm_amd.feature.feature_extract``
+    on the reference and every target image as one batch, or the module
+    itself; "auto" asks besides for the stock FeatureExtraction graph
+    (``feature_layout_ok``; an injected ``feature_fn`` never is) and a
+    quarter-resolution map of at least 32 x 32.  It resolves to "fp16"
+    because the HIP route measured faster (FEATURE_AUTO_HIP)."""
 
     def __init__(self, nlabel, mindepth=None, cfg=None, feature_fn=None, cost_dtype=torch.float32,
-                 conv_precision="auto", context_precision="auto", dep_context_precision="auto"):
+                 conv_precision="auto", context_precision="auto", dep_context_precision="auto",
+                 feature_precision="auto"):
         super().__init__(64)
         c = _default_cfg if cfg is None else cfg
         if c.get("COST_BY_COLOR", False) or c.get("COST_BY_COLOR_WITH_FEAT", False):
@@ -165,6 +183,9 @@ class PSNet(CostRegularization):
         if dep_context_precision not in ("auto", "torch", "fp16", "bf16"):
             raise ValueError(f"unknown dep_context precision {dep_context_precision!r}")
         self.dep_context_precision = dep_context_precision
+        if feature_precision not in ("auto", "torch", "fp16"):
+            raise ValueError(f"unknown feature precision {feature_precision!r}")
+        self.feature_precision = feature_precision
         self.feature_extraction = FeatureExtraction() if feature_fn is None else feature_fn
         if c.get("IND_CONTEXT", False):
             self.context_net = FeatureExtraction()
@@ -192,6 +213,27 @@ class PSNet(CostRegularization):
         (see ``dep_context_precision``; ``context_route``'s rule)."""
         return self._stack_route("dep_context_precision", "dep_convs", dep_stock_layout, device)
 
+    def feature_route(self, device=None, image_hw=None, name="feature_extraction"):
+        """How the feature CNN ``name`` ("feature_extraction" or
+        "context_net") runs at this call: "torch" or "fp16" (see
+        ``feature_precision``; ``context_route``'s rule, and for "auto" an
+        image whose quarter-resolution map is at least 32 x 32)."""
+        route = self._stack_route("feature_precision", name, _feature.feature_layout_ok, device)
+        if route == "fp16" and self.feature_precision == "auto":
+            if not FEATURE_AUTO_HIP or image_hw is None or min(_feature.feature_hw(image_hw)) < _feature.MIN_MAP:
+                return "torch"
+        return route
+
+    def _features(self, name, images):
+        """The feature CNN ``name`` on each of ``images``: on the HIP route as
+        one batch (every image is computed on its own), else the module per
+        image, as the reference calls it."""
+        net = getattr(self, name)
+        if self.feature_route(images[0].device, images[0].shape[2:], name) == "fp16":
+            n = [im.shape[0] for im in images]
+            return list(_feature.feature_extract(net, torch.cat(images) if len(images) > 1 else images[0]).split(n))
+        return [net(im) for im in images]
+
     def _stack_route(self, arg, name, layout_ok, device):
         p = getattr(self, arg)
         if p == "torch":
@@ -206,7 +248,9 @@ class PSNet(CostRegularization):
         # the HIP route calls no module, so it is taken only where self.convs(x) / self.dep_convs(x) would run
         # the stock stack and nothing else (the rule psnet_depth applies to the fused sweep)
         convs = getattr(self, name, None)
-        if convs is None or convs._forward_hooks or convs._forward_pre_hooks or not layout_ok(convs):
+        if not isinstance(convs, nn.Module):         # absent, or an injected feature_fn: never a stock module
+            return "torch"
+        if convs._forward_hooks or convs._forward_pre_hooks or not layout_ok(convs):
             return "torch"
         return "fp16"
 
@@ -217,14 +261,14 @@ class PSNet(CostRegularization):
             pose[:, 0, :, -1:] = pose[:, 0, :, -1:] * c.NORM_TARGET      # in place, PSNet.py:135-136
         pbd = bool(c.get("PREDICT_BY_DEPTH", False))
         fused = fused_channels_last(self.cost_dtype, self.conv_precision)
-        ref_raw = self.feature_extraction(ref)
+        ref_raw, *tgt_raws = self._features("feature_extraction", [ref] + list(targets))
         # the float32 copy of the reference features, made where something reads it: the sweep of anything but
         # float16 features on the fused route, the context stack, PSNET_DEP_CONTEXT
         ref_fea = None
         dep_src = ref_raw           # what PSNET_DEP_CONTEXT upsamples: refimg_fea as PSNet.py:219 finds it
         costs = None
         for j, target in enumerate(targets):
-            tgt_raw = self.feature_extraction(target)
+            tgt_raw = tgt_raws[j]
             if fused and f16_features(ref_raw, tgt_raw):
                 # MIXED_PREC: the fused sweep reads the float16 features as they come (the same bits)
                 r, t = ref_raw, tgt_raw
@@ -250,12 +294,12 @@ class PSNet(CostRegularization):
         if route in ("fp16", "bf16"):
             # the stack on libsfm_hip: the features in whatever dtype they arrive (no float32 copy), the planes
             # b-major, so the result is already the [B, L, h, w] volume the head reads
-            ctx = self.context_net(ref) if c.get("IND_CONTEXT", False) else ref_raw    # PSNet.py:177-178
+            ctx = self._features("context_net", [ref])[0] if c.get("IND_CONTEXT", False) else ref_raw  # 177-178
             dep_src = ctx
             costss = context_refine(self.convs, ctx, costs.float(), precision=route)
         elif route == "torch":
             if c.get("IND_CONTEXT", False):
-                ref_fea = self.context_net(ref).float()        # PSNet.py:177-178 reassigns refimg_fea
+                ref_fea = self._features("context_net", [ref])[0].float()      # PSNet.py:177-178 reassigns refimg_fea
                 dep_src = ref_fea
             elif ref_fea is None:
                 ref_fea = ref_raw.float()

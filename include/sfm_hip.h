@@ -632,6 +632,56 @@ int sfm_dep_context_pack_f16(const float* depth, const void* feat, int feat_dtyp
 int sfm_dep_context_pack_bf16(const float* depth, const void* feat, int feat_dtype, const float* image, int batch,
                               int b0, int nb, int channels, int h, int w, int H, int W, void* out, void* stream);
 
+/* One Conv2d of PSNet's feature CNN (models/submodule.py:11-15 convbn, 22-44
+ * BasicBlock with its downsample and "+= x", 108-184 feature_extraction), its
+ * BatchNorm2d folded (eval mode): sfm_conv2_f16 generalised to that layer set,
+ * on v_mfma_f32_32x32x16_f16 with fp32 accumulation:
+ *   out = f16round([relu](conv(in) * scale[co] + bias[co]) + residual)
+ *   in [dev] images x hin x win x cin float16 (channels-last), cin a multiple
+ *     of 32 from 32 to 320 (the image's 3 channels padded to 32, sfm_image_pack_f16);
+ *   ksize 3 or 1; stride 1 or 2; dilation 1..16, and 1 only for ksize 1 or
+ *     stride 2; zero padding of dilation (3 x 3) or 0 (1 x 1), so
+ *     hout = (hin - 1) / stride + 1 and wout = (win - 1) / stride + 1;
+ *   weights [dev] ksize^2 x cout x cin float16, tap = kh*ksize + kw;
+ *   cout 32, 64, 96 or 128; scale, bias [dev] cout float32;
+ *   residual [dev] images x hout x wout x cout float16 or NULL, added in fp32
+ *     before the one rounding (to nearest even); relu with a residual is refused;
+ *   out [dev] images x hout x wout x cout float16.
+ * At ksize 3, stride 1, residual NULL the result is sfm_conv2_f16's, bit for
+ * bit.  Every pointer 16-byte aligned; out aliases no input. */
+int sfm_conv2x_f16(const void* in, int images, int cin, int hin, int win, const void* weights, int cout, int ksize,
+                   int stride, int dilation, const float* scale, const float* bias, int relu, const void* residual,
+                   void* out, void* stream);
+
+/* The feature CNN's first input (models/submodule.py:112 firstconv's 3-channel
+ * convbn): image [dev] batch x 3 x h x w float32 -> out [dev] batch x h x w x 32
+ * float16, channels 0..2 the image (round to nearest even), 3..31 zero.
+ * Both pointers 16-byte aligned. */
+int sfm_image_pack_f16(const float* image, int batch, int h, int w, void* out, void* stream);
+
+/* The AvgPool2d of the feature CNN's pyramid branches (models/submodule.py:
+ * 125-139 branch1..4: kernel = stride = pool): in [dev] images x h x w x
+ * channels float16 (channels a multiple of 8, at most 2048) -> out [dev]
+ * images x h/pool x w/pool x channels float16 (both divisions floor; h, w >=
+ * pool), pool 4, 8, 16 or 32: the window summed in fp32, times 1 / pool^2,
+ * rounded once.  Both pointers 16-byte aligned. */
+int sfm_avgpool_f16(const void* in, int images, int h, int w, int channels, int pool, void* out, void* stream);
+
+/* lastconv's input (models/submodule.py:169-181: the four branches upsampled
+ * to the skip map's size, bilinear, align_corners=True, and
+ * cat((output_raw, output_skip, branch4, branch3, branch2, branch1), 1)):
+ *   raw [dev] images x h x w x 64, skip [dev] images x h x w x 128 float16;
+ *   branches [host] 4 device pointers in cat order (branch4, branch3, branch2,
+ *     branch1), map b images x branch_h[b] x branch_w[b] x 32 float16;
+ *     branch_h, branch_w [host] 4 ints, each >= 1 (a 1 x 1 map has scale 0);
+ *   out [dev] images x h x w x 320 float16: channels 0..63 raw, 64..191 skip,
+ *     192 + 32 b .. the branch b map at src = dst * (in - 1) / (out - 1),
+ *     interpolated in torch's order of operations in float64 and rounded once,
+ *     as sfm_dep_context_pack_f16 does.
+ * Every device pointer 16-byte aligned; out aliases no input. */
+int sfm_spp_pack_f16(const void* raw, const void* skip, const void* const* branches, const int* branch_h,
+                     const int* branch_w, int images, int h, int w, void* out, void* stream);
+
 /* Tuning knobs (process-wide; every key, its accepted values and default):
  *
  *   launch shape only -- outputs are bit-identical for every value:

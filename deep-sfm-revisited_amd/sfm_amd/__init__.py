@@ -4,7 +4,7 @@ Host-side mirror of the reference's operator interfaces over the C ABI of
 libsfm_hip.so (include/sfm_hip.h):
   ransac   batched RANSAC five-point (essential_matrix extension), flow -> points
   sweep    plane-sweep cost volume (planar, or channels-last for the regulariser), inverse_warp,
-           PSNet sweep section
+           PSNet sweep section; plane_sweep_cost_autograd / inverse_warp_autograd with a gradient into the features
   regularize  PSNet 3-D cost regularisation (dres0..classify) on the matrix cores
   synth    seeded synthetic KITTI-shaped inputs
   dist     one-process-per-GPU pair sharding and RCCL metric gather
@@ -12,4 +12,13 @@ libsfm_hip.so (include/sfm_hip.h):
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["ransac", "sweep", "regularize", "synth", "dist", "config", "validate"]
+__all__ = ["ransac", "sweep", "regularize", "synth", "dist", "config", "validate", "plane_sweep_cost_autograd",
+           "inverse_warp_autograd"]
+
+
+def __getattr__(name):
+    # the differentiable sweep entries, imported on first use (sfm_amd.sweep needs torch)
+    if name in ("plane_sweep_cost_autograd", "inverse_warp_autograd"):
+        from . import sweep
+        return getattr(sweep, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -98,6 +98,13 @@ _SIGS = [
       ctypes.c_float, ctypes.c_float, _c_dp, _c_dp]),
     ("sfm_inverse_warp", ctypes.c_int,
      [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    ("sfm_plane_sweep_backward_workspace_bytes", ctypes.c_size_t,
+     [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    ("sfm_plane_sweep_backward", ctypes.c_int,
+     [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp, ctypes.c_int,
+      ctypes.c_float, ctypes.c_int, _c_dp, _c_dp, _c_dp, ctypes.c_size_t, _c_dp]),
+    ("sfm_inverse_warp_backward", ctypes.c_int,
+     [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     ("sfm_kinv3x3", ctypes.c_int, [_c_dp, ctypes.c_int, _c_dp, _c_dp]),
     ("sfm_flow2depth", ctypes.c_int, [_c_dp, _c_dp, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp]),
     ("sfm_depth_metrics_workspace_bytes", ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),

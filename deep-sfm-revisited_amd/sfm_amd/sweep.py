@@ -4,6 +4,9 @@
   (cost[:, :C, i] = ref, cost[:, C:, i] = inverse_warp(tgt, d_i)) with one
   kernel launch.
 * ``inverse_warp``     — drop-in for models/inverse_warp.py:121-153.
+* ``plane_sweep_cost_autograd``, ``inverse_warp_autograd`` — the same two with a
+  gradient into the features (sfm_plane_sweep_backward,
+  sfm_inverse_warp_backward), for the reference's training loop.
 * ``PlaneSweep``       — the sweep section of PSNet.forward (PSNet.py:130-158):
   K/4 rows 0-1, K^-1[:2,:2]*4, optional RESCALE_DEPTH translation scaling (in
   place on the caller's pose tensor, as the reference does), one cost volume
@@ -29,8 +32,22 @@ def _refuse_grad(**tensors):
         return
     for name, t in tensors.items():
         if t is not None and t.requires_grad:
-            raise RuntimeError(f"{name} requires grad, but the HIP plane sweep is forward-only (no backward "
-                               f"kernel); run it under torch.no_grad() or detach the input")
+            raise RuntimeError(f"{name} requires grad, but this entry of the HIP plane sweep is forward-only (no "
+                               f"backward kernel); run it under torch.no_grad() or detach the input, or, for a "
+                               f"gradient into the features, call sfm_amd.sweep.plane_sweep_cost_autograd / "
+                               f"inverse_warp_autograd")
+
+
+def _refuse_geometry_grad(**tensors):
+    """The backward kernel forms the gradient into the features only.  The
+    reference detaches the RANSAC pose (SFMnet.py:267, 272) and PSNet's plane
+    depths are constants, so nothing it trains needs the others."""
+    if not torch.is_grad_enabled():
+        return
+    for name, t in tensors.items():
+        if t is not None and t.requires_grad:
+            raise RuntimeError(f"{name} requires grad, but the HIP plane sweep differentiates with respect to the "
+                               f"features only; detach {name}")
 
 
 def check_sizes(t, name, expected):
@@ -231,6 +248,112 @@ def inverse_warp(feat, depth, pose, intrinsics, intrinsics_inv, padding_mode="ze
     return out
 
 
+def backward_workspace_for(batch, channels, h, w, nlabel, device):
+    """Scratch of sfm_plane_sweep_backward (per-pair projections, plane depths)."""
+    n = _lib.load().sfm_plane_sweep_backward_workspace_bytes(int(batch), int(channels), int(h), int(w), int(nlabel))
+    return torch.empty(int(n), dtype=torch.uint8, device=device)
+
+
+class _PlaneSweepCost(torch.autograd.Function):
+    """plane_sweep_cost (float32) with sfm_plane_sweep_backward as its backward."""
+
+    @staticmethod
+    def forward(ctx, ref, tgt, pose, K4, Ki4, nlabel, min_depth, warped_only, predict_by_depth):
+        # grad mode is off in here: plane_sweep_cost's own checks and launch (sfm_plane_sweep_ex), the same bits
+        cost = plane_sweep_cost(ref, tgt, pose, K4, Ki4, nlabel, min_depth, torch.float32, warped_only=warped_only,
+                                predict_by_depth=predict_by_depth)
+        ctx.save_for_backward(pose, K4, Ki4)
+        ctx.sweep = (tuple(tgt.shape), int(nlabel), float(min_depth), bool(warped_only), bool(predict_by_depth))
+        return cost
+
+    @staticmethod
+    def backward(ctx, g):
+        pose, K4, Ki4 = ctx.saved_tensors
+        (B, C, h, w), nlabel, min_depth, warped_only, by_depth = ctx.sweep
+        g = g.contiguous().float()
+        want_ref = (not warped_only) and ctx.needs_input_grad[0]
+        grad_ref = torch.empty((B, C, h, w), dtype=torch.float32, device=g.device) if want_ref else None
+        grad_tgt = torch.empty((B, C, h, w), dtype=torch.float32, device=g.device)
+        ws = backward_workspace_for(B, C, h, w, nlabel, g.device)
+        with torch.cuda.device(g.device):
+            rc = _lib.load().sfm_plane_sweep_backward(_lib.ptr(g), 1 if warped_only else 0, B, C, h, w, _lib.ptr(pose),
+                                                      _lib.ptr(K4), _lib.ptr(Ki4), nlabel, min_depth,
+                                                      1 if by_depth else 0, _lib.ptr(grad_ref), _lib.ptr(grad_tgt),
+                                                      _lib.ptr(ws), ws.numel(), _lib.stream_ptr(g.device))
+            _lib.check(rc, "sfm_plane_sweep_backward")
+        return grad_ref, grad_tgt, None, None, None, None, None, None, None
+
+
+def plane_sweep_cost_autograd(ref_fea, tgt_fea, pose, intrinsics4, intrinsics_inv4, nlabel, min_depth=1.0,
+                              warped_only=False, predict_by_depth=False):
+    """``plane_sweep_cost`` (float32 volume, the same bits) with a gradient into
+    the features, as the reference's training loop forms it through
+    cost[:, :C, i] = ref and grid_sample (PSNet.py:155, inverse_warp.py:151):
+    one sfm_plane_sweep_backward call, the exact transpose of the forward's taps.
+    Only ``ref_fea`` and ``tgt_fea`` get a gradient; float16 features are widened
+    on the way in and their gradient comes back in float16.  ``pose`` or the
+    intrinsics requiring grad is refused.  The target gradient is accumulated
+    with float atomics and may differ in its last bits from run to run, like
+    torch's grid_sample backward on the GPU; the reference gradient is
+    reproducible."""
+    _refuse_geometry_grad(pose=pose, intrinsics4=intrinsics4, intrinsics_inv4=intrinsics_inv4)
+    tgt = _dev_f32(tgt_fea, "tgt_fea")
+    B = tgt.shape[0]
+    ref = None if warped_only else _dev_f32(ref_fea, "ref_fea")
+    P = _dev_f32(pose.reshape(B, 3, 4), "pose")
+    K4 = _dev_f32(intrinsics4.reshape(B, 3, 3), "intrinsics")
+    Ki4 = _dev_f32(intrinsics_inv4.reshape(B, 3, 3), "intrinsics_inv")
+    return _PlaneSweepCost.apply(ref, tgt, P, K4, Ki4, int(nlabel), float(min_depth), bool(warped_only),
+                                 bool(predict_by_depth))
+
+
+class _InverseWarp(torch.autograd.Function):
+    """inverse_warp with sfm_inverse_warp_backward as its backward."""
+
+    @staticmethod
+    def forward(ctx, feat, depth, pose, K, Kinv):
+        out = inverse_warp(feat, depth, pose, K, Kinv)
+        ctx.save_for_backward(depth, pose, K, Kinv)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        depth, pose, K, Kinv = ctx.saved_tensors
+        g = g.contiguous().float()
+        B, C, h, w = g.shape
+        grad = torch.empty_like(g)
+        with torch.cuda.device(g.device):
+            rc = _lib.load().sfm_inverse_warp_backward(_lib.ptr(g), B, C, h, w, _lib.ptr(depth), _lib.ptr(pose),
+                                                       _lib.ptr(K), _lib.ptr(Kinv), _lib.ptr(grad),
+                                                       _lib.stream_ptr(g.device))
+            _lib.check(rc, "sfm_inverse_warp_backward")
+        return grad, None, None, None, None
+
+
+def inverse_warp_autograd(feat, depth, pose, intrinsics, intrinsics_inv, padding_mode="zeros"):
+    """``inverse_warp`` (the same output bits) with a gradient into ``feat``
+    (sfm_inverse_warp_backward): the drop-in for the reference's training loop,
+    ``from sfm_amd.sweep import inverse_warp_autograd as inverse_warp``.
+    ``depth``, ``pose`` or the intrinsics requiring grad is refused.  The
+    gradient is accumulated with float atomics and may differ in its last bits
+    from run to run, like torch's grid_sample backward on the GPU."""
+    check_sizes(depth, "depth", "BHW")
+    check_sizes(pose, "pose", "B34")
+    check_sizes(intrinsics, "intrinsics", "B33")
+    check_sizes(intrinsics_inv, "intrinsics", "B33")
+    assert intrinsics_inv.size() == intrinsics.size()
+    if padding_mode != "zeros":
+        raise NotImplementedError("only padding_mode='zeros' is on the plane-sweep path")
+    _refuse_geometry_grad(depth=depth, pose=pose, intrinsics=intrinsics, intrinsics_inv=intrinsics_inv)
+    f = _dev_f32(feat, "feat")
+    B, C, h, w = f.shape
+    if tuple(depth.shape) != (B, h, w) or pose.size(0) != B or intrinsics.size(0) != B:
+        raise RuntimeError(f"inverse_warp: depth {tuple(depth.shape)}, pose {tuple(pose.shape)} and intrinsics "
+                           f"{tuple(intrinsics.shape)} must match feat {(B, C, h, w)}")
+    return _InverseWarp.apply(f, _dev_f32(depth, "depth"), _dev_f32(pose, "pose"), _dev_f32(intrinsics, "intrinsics"),
+                              _dev_f32(intrinsics_inv, "intrinsics_inv"))
+
+
 def quarter_intrinsics(intrinsics, intrinsics_inv):
     """PSNet.py:130-133: K/4 on rows 0-1; K^-1 with [:2,:2]*4."""
     K4 = intrinsics.clone()
@@ -241,11 +364,16 @@ def quarter_intrinsics(intrinsics, intrinsics_inv):
 
 
 class PlaneSweep(torch.nn.Module):
-    """Sweep section of PSNet.forward (models/PSNet.py:128-158) on given features."""
+    """Sweep section of PSNet.forward (models/PSNet.py:128-158) on given features.
+    ``differentiable``: the float32 volume with a gradient into the features
+    (plane_sweep_cost_autograd); the default stays forward-only."""
 
     def __init__(self, nlabel, mindepth=1.0, rescale_depth=False, norm_target=0.8, dtype=torch.float32,
-                 predict_by_depth=False):
+                 predict_by_depth=False, differentiable=False):
         super().__init__()
+        if differentiable and dtype != torch.float32:
+            raise RuntimeError("the differentiable plane sweep writes a float32 volume")
+        self.differentiable = bool(differentiable)
         self.predict_by_depth = predict_by_depth
         self.nlabel = int(nlabel)
         self.mindepth = float(mindepth)
@@ -259,6 +387,11 @@ class PlaneSweep(torch.nn.Module):
         K4, Ki4 = quarter_intrinsics(intrinsics, intrinsics_inv)
         if self.rescale_depth:
             pose[:, 0, :, -1:] = pose[:, 0, :, -1:] * self.norm_target
+        if self.differentiable:
+            # a gradient into the features (plane_sweep_cost_autograd), for training
+            return [plane_sweep_cost_autograd(ref_fea, t, pose[:, j], K4, Ki4, self.nlabel, self.mindepth,
+                                              predict_by_depth=self.predict_by_depth)
+                    for j, t in enumerate(tgt_feas)]
         return [plane_sweep_cost(ref_fea, t, pose[:, j], K4, Ki4, self.nlabel, self.mindepth, self.dtype,
                                  predict_by_depth=self.predict_by_depth)
                 for j, t in enumerate(tgt_feas)]

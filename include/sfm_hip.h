@@ -396,6 +396,33 @@ int sfm_plane_sweep_warped(const float* tgt, int batch, int channels, int h, int
                            int nlabel, float min_depth, int out_dtype, void* out,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* Backward of the cost volume of models/PSNet.py:144-157 into the features:
+ * what autograd computes in the reference's training loop through
+ * cost[:, :C, i] = ref (PSNet.py:155) and through F.grid_sample inside
+ * inverse_warp (models/inverse_warp.py:151) into the target features.
+ *   grad_ref[b, c, p] = sum_i grad_cost[b, c, i, p]
+ *   grad_tgt[b, c, t] = sum_i sum_p sum_k [tap_k(b, i, p) == t] weight_k(b, i, p) grad_cost[b, C + c, i, p]
+ * with the taps and weights of the forward (the same float32 bits), so the
+ * result is the exact transpose of sfm_plane_sweep_ex's warped half.  No
+ * gradient is formed for pose, K4, K4inv or the plane depths.
+ *   grad_cost  [dev] batch x 2C x nlabel x h x w float32 (planar), or
+ *              batch x C x nlabel x h x w with warped_only = 1
+ *   grad_ref   [dev] batch x C x h x w float32, or NULL (not wanted); must be
+ *              NULL with warped_only
+ *   grad_tgt   [dev] batch x C x h x w float32; zeroed inside the call
+ *   pose, K4, K4inv, nlabel, min_depth as sfm_plane_sweep_ex; predict_by_depth
+ *              is its depth_mode
+ *   workspace  sfm_plane_sweep_backward_workspace_bytes(batch, channels, h, w, nlabel)
+ * Every buffer 4-byte aligned.  nlabel * h < 2^31, w < 2^23.
+ * grad_tgt is accumulated with float atomics and may differ in its last bits
+ * between two calls on the same inputs (as torch's grid_sample backward on the
+ * GPU); grad_ref is reproducible bit for bit. */
+size_t sfm_plane_sweep_backward_workspace_bytes(int batch, int channels, int h, int w, int nlabel);
+int sfm_plane_sweep_backward(const float* grad_cost, int warped_only, int batch, int channels, int h, int w,
+                             const float* pose, const float* K4, const float* K4inv, int nlabel, float min_depth,
+                             int predict_by_depth, float* grad_ref /* may be null */, float* grad_tgt,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * Depth stage after the sweep
  * ------------------------------------------------------------------------ */
@@ -433,6 +460,16 @@ int sfm_kinv3x3(const float* K, int batch, float* Kinv, void* stream);
 int sfm_inverse_warp(const float* feat, int batch, int channels, int h, int w,
                      const float* depth, const float* pose, const float* K, const float* Kinv,
                      float* out, void* stream);
+
+/* Backward of sfm_inverse_warp into feat: the gradient autograd forms through
+ * F.grid_sample at models/inverse_warp.py:151 (the reference's per-plane callers:
+ * PSNet.py:155, PANet.py:129, REGNet.py:177, REG2D.py:108,139), as the exact
+ * transpose of the forward's taps and weights.  No gradient for depth, pose, K.
+ *   grad_out [dev] B x C x h x w float32; depth, pose, K, Kinv as sfm_inverse_warp;
+ *   grad_feat [dev] B x C x h x w float32, zeroed inside the call.
+ * Float atomics: last bits may differ from call to call (sfm_plane_sweep_backward). */
+int sfm_inverse_warp_backward(const float* grad_out, int batch, int channels, int h, int w, const float* depth,
+                              const float* pose, const float* K, const float* Kinv, float* grad_feat, void* stream);
 
 /* Flow2Depth, models/flow2depth.py:7-41 (dead code in the reference):
  *   KR = K.R [dev] B x 3 x 3, KT = K.T [dev] B x 3, Kinv [dev] B x 3 x 3
@@ -809,7 +846,10 @@ const char* sfm_last_scorer(void);
  *                        or a shape outside the other forms' range)
  *   "k_sweep"            the per-row form with element stores
  * sfm_plane_sweep_cl, _cl_f16: "k_sweep_cl" (the fast path) or "k_sweep_cl_any";
- * sfm_plane_sweep_ref_planes: "k_ref_planes" or "k_ref_planes_generic". */
+ * sfm_plane_sweep_ref_planes: "k_ref_planes" or "k_ref_planes_generic";
+ * sfm_plane_sweep_backward, sfm_inverse_warp_backward: "k_sweep_bwd" (an LDS
+ * window of target rows per workgroup, flushed with row-contiguous atomics) or
+ * "k_sweep_bwd+global" (rows too long for a window: every tap a global atomic). */
 const char* sfm_last_sweep(void);
 
 /* ------------------------------------------------------------------------

@@ -17,6 +17,7 @@
 // loads per pixel and plane, from L2), the head reads the low-resolution cost
 // from L2 (15 MB per KITTI pair at L=128) and writes 4 bytes per output pixel.
 #include <string>
+#include "depth_head.h"
 #include "warp.h"
 
 namespace sfm {
@@ -73,41 +74,6 @@ __global__ __launch_bounds__(kCorrThreads) void k_sweep_corr(const f32x4* __rest
     // outside the image the warped features are 0, so the product is 0
     out[((size_t)b * L + l) * hw + p] = acc / (float)C;
   }
-}
-
-struct HeadTaps {
-  int o00, o01, o10, o11;
-  double wx0, wx1, wy0, wy1;
-};
-
-// F.interpolate(..., mode='trilinear', align_corners=False) source index and
-// weights along one axis (PyTorch's area_pixel_compute_source_index with
-// guard_index_and_lambda; identity when the sizes match).  In float64: a
-// float32 weight is off by about 1e-6, and the classify logits differ by
-// O(100) between neighbouring taps, which moved the soft-argmin by up to 2e-4
-// of the depth against the exact interpolation (tests/test_gpu_depth.py).
-__device__ __forceinline__ void axis_weights(int dst, int in_size, int out_size, double ratio, int& i0, int& i1,
-                                             double& l0, double& l1) {
-  if (in_size == out_size) {
-    i0 = i1 = dst;
-    l0 = 1.0;
-    l1 = 0.0;
-    return;
-  }
-  double src = ratio * ((double)dst + 0.5) - 0.5;
-  if (src < 0.0) src = 0.0;
-  i0 = min((int)floor(src), in_size - 1);
-  l1 = fmin(fmax(src - (double)i0, 0.0), 1.0);
-  i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-  l0 = 1.0 - l1;
-}
-
-// interpolated cost of plane l (PyTorch's nested order: ((x00 wx0 + x01 wx1) wy0 + (x10 wx0 + x11 wx1) wy1)),
-// float32 taps combined in float64
-__device__ __forceinline__ double head_value(const float* __restrict__ plane, const HeadTaps& t) {
-  const double r0 = (double)plane[t.o00] * t.wx0 + (double)plane[t.o01] * t.wx1;
-  const double r1 = (double)plane[t.o10] * t.wx0 + (double)plane[t.o11] * t.wx1;
-  return r0 * t.wy0 + r1 * t.wy1;
 }
 
 // grid (ceil(W / 256), H, B); thread = output pixel

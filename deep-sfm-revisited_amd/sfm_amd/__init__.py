@@ -6,6 +6,7 @@ libsfm_hip.so (include/sfm_hip.h):
   sweep    plane-sweep cost volume (planar, or channels-last for the regulariser), inverse_warp,
            PSNet sweep section; plane_sweep_cost_autograd / inverse_warp_autograd with a gradient into the features
   regularize  PSNet 3-D cost regularisation (dres0..classify) on the matrix cores
+  depth    correlation cost and the soft-argmin depth head; depth_head_autograd with a gradient into the cost
   synth    seeded synthetic KITTI-shaped inputs
   dist     one-process-per-GPU pair sharding and RCCL metric gather
   validate the validation loop and its fused depth-metric rows (main.py:477-601)
@@ -13,12 +14,15 @@ libsfm_hip.so (include/sfm_hip.h):
 from . import _lib  # noqa: F401
 
 __all__ = ["ransac", "sweep", "regularize", "synth", "dist", "config", "validate", "plane_sweep_cost_autograd",
-           "inverse_warp_autograd"]
+           "inverse_warp_autograd", "depth_head_autograd"]
 
 
 def __getattr__(name):
-    # the differentiable sweep entries, imported on first use (sfm_amd.sweep needs torch)
+    # the differentiable entries, imported on first use (sfm_amd.sweep and sfm_amd.depth need torch)
     if name in ("plane_sweep_cost_autograd", "inverse_warp_autograd"):
         from . import sweep
         return getattr(sweep, name)
+    if name == "depth_head_autograd":
+        from . import depth
+        return depth.depth_head_autograd
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -96,6 +96,12 @@ _SIGS = [
     ("sfm_depth_head", ctypes.c_int,
      [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
       ctypes.c_float, ctypes.c_float, _c_dp, _c_dp]),
+    ("sfm_depth_head_backward_workspace_bytes", ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    ("sfm_depth_head_backward", ctypes.c_int,
+     [_c_dp, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+      ctypes.c_float, ctypes.c_float, _c_dp, _c_dp, ctypes.c_size_t, _c_dp]),
+    ("sfm_depth_head_contributors", ctypes.c_int,
+     [ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 4),
     ("sfm_inverse_warp", ctypes.c_int,
      [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     ("sfm_plane_sweep_backward_workspace_bytes", ctypes.c_size_t,

@@ -5,11 +5,14 @@
   the [B, C, L, h, w] warped volume.
 * ``depth_head``       — PSNet.py:191-213 soft-argmin head: trilinear upsample
   of a [B, L, h, w] (or [B, 1, L, h, w]) cost to the image size, softmax over
-  planes, disparity / depth regression (submodule.py:57-93).
+  planes, disparity / depth regression (submodule.py:57-93).  Forward only.
+* ``depth_head_autograd`` — the same head with a gradient into the cost
+  (sfm_depth_head_backward), for the reference's training loop.
 * ``CorrelationDepth`` — correlation cost + head: a parameter-free depth map
   from (ref_fea, tgt_fea, pose) at image resolution.
 """
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .sweep import quarter_intrinsics
@@ -56,7 +59,10 @@ def correlation_cost(ref_fea, tgt_fea, pose, intrinsics4, intrinsics_inv4, nlabe
 def depth_head(cost, nlabel, min_depth=1.0, out_hw=None, predict_by_depth=False, out=None, scale=None):
     """Soft-argmin depth [B, 1, H, W] float32 from a cost [B, L, h, w] / [B, 1, L, h, w].
     ``scale`` (predict_by_depth only) replaces the final ``* min_depth``: PSNet's
-    depth_init is depthregression's output without it (PSNet.py:200-202)."""
+    depth_init is depthregression's output without it (PSNet.py:200-202).
+    Forward only: the result has no autograd link, and a cost that requires
+    grad loses its gradient here without an error (kept as it always was);
+    ``depth_head_autograd`` is the head with a backward."""
     c = _dev_f32(cost, "cost")
     if c.dim() == 5:
         if c.shape[1] != 1:
@@ -79,6 +85,66 @@ def depth_head(cost, nlabel, min_depth=1.0, out_hw=None, predict_by_depth=False,
                                         mul, step, _lib.ptr(out), _lib.stream_ptr(c.device))
         _lib.check(rc, "sfm_depth_head")
     return out
+
+
+def head_backward_workspace_for(batch, H, W, device):
+    """Scratch of sfm_depth_head_backward (three float64 per output pixel)."""
+    n = _lib.load().sfm_depth_head_backward_workspace_bytes(int(batch), int(H), int(W))
+    return torch.empty(int(n), dtype=torch.uint8, device=device)
+
+
+class _DepthHead(torch.autograd.Function):
+    """depth_head with sfm_depth_head_backward as its backward."""
+
+    @staticmethod
+    def forward(ctx, cost, nlabel, min_depth, out_hw, predict_by_depth, scale):
+        # grad mode is off in here: depth_head's own checks and launch (sfm_depth_head), the same bits
+        depth = depth_head(cost, nlabel, min_depth, out_hw, predict_by_depth, scale=scale)
+        ctx.save_for_backward(cost)
+        ctx.head = (int(depth.shape[2]), int(depth.shape[3]), float(min_depth), bool(predict_by_depth), scale)
+        return depth
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None
+        cost, = ctx.saved_tensors
+        H, W, min_depth, by_depth, scale = ctx.head
+        B, L, h, w = cost.shape
+        g = g.contiguous().float()
+        # the forward's multiplier and step (depth_head)
+        mul = min_depth if (scale is None or not by_depth) else float(scale)
+        step = float(int(min_depth)) if by_depth else 0.0
+        grad_cost = torch.empty_like(cost)
+        ws = head_backward_workspace_for(B, H, W, g.device)
+        with torch.cuda.device(g.device):
+            rc = _lib.load().sfm_depth_head_backward(_lib.ptr(cost), _lib.ptr(g), B, L, h, w, H, W,
+                                                     1 if by_depth else 0, mul, step, _lib.ptr(grad_cost),
+                                                     _lib.ptr(ws), ws.numel(), _lib.stream_ptr(g.device))
+            _lib.check(rc, "sfm_depth_head_backward")
+        return grad_cost, None, None, None, None, None
+
+
+def depth_head_autograd(cost, nlabel, min_depth=1.0, out_hw=None, predict_by_depth=False, scale=None):
+    """``depth_head`` (the same bits) with a gradient into ``cost``, as the
+    reference's training loop forms it through F.interpolate, softmax and
+    disparityregression / depthregression (PSNet.py:194-216,
+    submodule.py:57-93): one sfm_depth_head_backward call, the exact transpose of
+    the forward, reproducible bit for bit (a gather, no atomics).  Only ``cost``
+    gets a gradient.  A float16 or 5-D cost is widened and reshaped by torch ops
+    out here, so its gradient comes back in its own dtype and shape."""
+    if not cost.is_cuda:
+        raise RuntimeError("cost must be a CUDA tensor")
+    c = cost
+    if c.dim() == 5:
+        if c.shape[1] != 1:
+            raise RuntimeError("a 5-D cost must have one channel (the classify output)")
+        c = c[:, 0]
+    c = c.float().contiguous()
+    hw = None if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+    return _DepthHead.apply(c, int(nlabel), float(min_depth), hw, bool(predict_by_depth),
+                            None if scale is None else float(scale))
 
 
 class CorrelationDepth(torch.nn.Module):

@@ -17,6 +17,9 @@ and runs its forward with the hot path on libsfm_hip:
   convs               per-plane context CNN (PSNET_CONTEXT, 175-192)   sfm_conv2_* (HIP MFMA) under float16 autocast
                       in eval mode (``context_precision``); else       torch (MIOpen)
   head                trilinear up, softmax, disparity regression     sfm_depth_head (HIP)
+  training            grad mode on, features that require grad:        sfm_plane_sweep_ex / _backward and
+                      the sweep and both heads with a backward,        sfm_depth_head / _backward (HIP);
+                      the stacks as the nn.Modules they are            torch (MIOpen)
   dep_convs           full-resolution depth refinement (PSNET_DEP_CONTEXT, 218-225): bilinear upsample + cat
                       sfm_dep_context_pack_* (HIP), the stack      sfm_conv2_* (HIP MFMA) under float16 autocast
                       in eval mode (``dep_context_precision``); else   torch (MIOpen)
@@ -34,14 +37,33 @@ import torch.nn.functional as F
 from . import feature as _feature
 from .config import cfg as _default_cfg
 from .context import context_refine, dep_context_refine, dep_stock_layout, stock_layout
-from .depth import depth_head
+from .depth import depth_head, depth_head_autograd
 from .regularize import CostRegularization, f16_features, fused_channels_last, sweep_regularize_fused
-from .sweep import plane_sweep_cost, quarter_intrinsics
+from .sweep import plane_sweep_cost, plane_sweep_cost_autograd, quarter_intrinsics
 
 
 # Whether feature_precision="auto" may resolve to "fp16": the same-process A/B of scripts/feature_ab.py decides it
 # (profiles/feature_ab.txt: HIP 2.246 ms, torch float16 autocast 7.043 ms per KITTI pair of images)
 FEATURE_AUTO_HIP = True
+
+# Whether the differentiable route's heads are depth_head_autograd (sfm_depth_head + sfm_depth_head_backward) or
+# torch_depth_head: the same-process A/B of scripts/depth_head_bwd_ab.py decides it (profiles/depth_head_bwd_ab.txt)
+HEAD_BWD_HIP = True
+
+
+def torch_depth_head(cost, nlabel, min_depth, out_hw, predict_by_depth=False, scale=None):
+    """PSNet.py:194-216 in torch ops on a [B, L, h, w] cost, float32: trilinear
+    upsample, softmax over planes, disparity / depth regression
+    (submodule.py:57-93).  ``depth_head``'s arguments; what the differentiable
+    route runs with HEAD_BWD_HIP off, and the torch arm of the A/B."""
+    L = int(nlabel)
+    up = F.interpolate(cost.float().unsqueeze(1), [L, int(out_hw[0]), int(out_hw[1])], mode="trilinear")[:, 0]
+    prob = F.softmax(up, dim=1)
+    idx = torch.arange(1, L + 1, dtype=torch.float32, device=cost.device).reshape(1, L, 1, 1)
+    if predict_by_depth:
+        mul = float(min_depth) if scale is None else float(scale)
+        return torch.sum(prob * (idx * float(int(min_depth))), 1, keepdim=True) * mul
+    return float(min_depth) * L / (torch.sum(prob * idx, 1, keepdim=True) + 1e-16)
 
 
 def _autocast_gpu_dtype():
@@ -159,7 +181,23 @@ class PSNet(CostRegularization):
     itself; "auto" asks besides for the stock FeatureExtraction graph
     (``feature_layout_ok``; an injected ``feature_fn`` never is) and a
     quarter-resolution map of at least 32 x 32.  It resolves to "fp16"
-    because the HIP route measured faster (FEATURE_AUTO_HIP)."""
+    because the HIP route measured faster (FEATURE_AUTO_HIP).
+
+    Training.  With grad mode on and features that require grad (every
+    training step, and an eval-mode call outside ``torch.no_grad()`` whose
+    features come from a torch module) ``forward`` takes the differentiable
+    route, the reference's graph with the sweep and both heads on libsfm_hip:
+    ``plane_sweep_cost_autograd`` on the float32 planar volume; ``dres0..4``
+    and ``classify`` as the modules they are (PSNet.py:160-165; BatchNorm
+    follows ``self.training``, as in torch); the context stack's and
+    ``dep_convs``' torch branches (on ``depth.detach()``, as the reference);
+    ``depth_head_autograd`` for ``depth_init`` and ``depth`` (HEAD_BWD_HIP; the
+    bits of ``depth_head``).  ``conv_precision`` and ``cost_dtype`` apply to
+    the forward-only route alone; a forced "fp16" / "bf16" context,
+    dep-context or feature precision has no backward and raises there.
+    Everything else is unchanged bit for bit: calls under ``torch.no_grad()``
+    in either mode, and the float16 eval routes, whose HIP features carry no
+    grad and so never enter the differentiable route."""
 
     def __init__(self, nlabel, mindepth=None, cfg=None, feature_fn=None, cost_dtype=torch.float32,
                  conv_precision="auto", context_precision="auto", dep_context_precision="auto",
@@ -254,6 +292,34 @@ class PSNet(CostRegularization):
             return "torch"
         return "fp16"
 
+    def _grad_stack_route(self, arg, route_fn, device):
+        """The differentiable route runs ``convs`` / ``dep_convs`` as the
+        modules they are ("torch"); a forced HIP precision has no backward, so
+        it is refused (in training mode with ``_stack_route``'s own message)."""
+        p = getattr(self, arg)
+        if p in ("fp16", "bf16"):
+            route_fn(device)
+            raise RuntimeError(f"{arg}={p!r} folds BatchNorm2d and has no backward, but the features require grad: "
+                               f"run under torch.no_grad(), or leave {arg} at 'auto' or 'torch'")
+        return "torch"
+
+    def _regularize_modules(self, cost):
+        """dres0..4 and classify as PSNet.py:160-165 calls them: the modules themselves, which carry a gradient
+        and whose BatchNorm follows self.training (the matrix-core stack folds it and has no backward)."""
+        c0 = self.dres0(cost)
+        for i in range(1, 5):
+            c0 = getattr(self, f"dres{i}")(c0) + c0
+        return self.classify(c0)
+
+    def _head(self, differentiable, cost, H, W, pbd, scale=None):
+        """The soft-argmin head on a [B, L, h, w] cost: ``depth_head``, or on the differentiable route
+        ``depth_head_autograd`` (the same bits) or, with HEAD_BWD_HIP off, PSNet.py:194-216 in torch ops."""
+        if not differentiable:
+            return depth_head(cost, self.nlabel, self.mindepth, (H, W), pbd, scale=scale)
+        if HEAD_BWD_HIP:
+            return depth_head_autograd(cost, self.nlabel, self.mindepth, (H, W), pbd, scale=scale)
+        return torch_depth_head(cost, self.nlabel, self.mindepth, (H, W), pbd, scale=scale)
+
     def forward(self, ref, targets, pose, intrinsics, intrinsics_inv, pose_gt=None, depth_gt=None, E_mat=None):
         c = self.cfg
         K4, Ki4 = quarter_intrinsics(intrinsics.float(), intrinsics_inv.float())
@@ -262,6 +328,8 @@ class PSNet(CostRegularization):
         pbd = bool(c.get("PREDICT_BY_DEPTH", False))
         fused = fused_channels_last(self.cost_dtype, self.conv_precision)
         ref_raw, *tgt_raws = self._features("feature_extraction", [ref] + list(targets))
+        # the differentiable route (see the class docstring): grad mode on and features that require grad
+        diff = torch.is_grad_enabled() and any(f.requires_grad for f in [ref_raw] + tgt_raws)
         # the float32 copy of the reference features, made where something reads it: the sweep of anything but
         # float16 features on the fused route, the context stack, PSNET_DEP_CONTEXT
         ref_fea = None
@@ -269,6 +337,14 @@ class PSNet(CostRegularization):
         costs = None
         for j, target in enumerate(targets):
             tgt_raw = tgt_raws[j]
+            if diff:
+                # sweep and stack with a backward: the float32 planar volume, then the modules themselves
+                ref_fea = ref_raw.float() if ref_fea is None else ref_fea
+                cost = plane_sweep_cost_autograd(ref_fea, tgt_raw.float(), pose[:, j].float(), K4, Ki4, self.nlabel,
+                                                 self.mindepth, predict_by_depth=pbd)
+                c0 = self._regularize_modules(cost)
+                costs = c0 if costs is None else costs + c0
+                continue
             if fused and f16_features(ref_raw, tgt_raw):
                 # MIXED_PREC: the fused sweep reads the float16 features as they come (the same bits)
                 r, t = ref_raw, tgt_raw
@@ -290,7 +366,10 @@ class PSNet(CostRegularization):
         B, _, L, h, w = costs.shape
         H, W = ref.shape[2], ref.shape[3]
         costss = costs
-        route = self.context_route(costs.device) if c.get("PSNET_CONTEXT", True) else None
+        route = None
+        if c.get("PSNET_CONTEXT", True):
+            route = self._grad_stack_route("context_precision", self.context_route, costs.device) if diff else \
+                self.context_route(costs.device)
         if route in ("fp16", "bf16"):
             # the stack on libsfm_hip: the features in whatever dtype they arrive (no float32 copy), the planes
             # b-major, so the result is already the [B, L, h, w] volume the head reads
@@ -310,11 +389,11 @@ class PSNet(CostRegularization):
             costss = (self.convs(x) + planes).reshape(L, B, h, w).permute(1, 0, 2, 3).unsqueeze(1)
         # PREDICT_BY_DEPTH: depth_init is depthregression's output unscaled,
         # depth is scaled by mindepth (PSNet.py:200-202 vs 209-210)
-        depth_init = depth_head(costs.reshape(B, L, h, w).contiguous(), self.nlabel, self.mindepth, (H, W), pbd,
-                                scale=1.0 if pbd else None)
-        depth = depth_head(costss.reshape(B, L, h, w).contiguous(), self.nlabel, self.mindepth, (H, W), pbd)
+        depth_init = self._head(diff, costs.reshape(B, L, h, w).contiguous(), H, W, pbd, scale=1.0 if pbd else None)
+        depth = self._head(diff, costss.reshape(B, L, h, w).contiguous(), H, W, pbd)
         if c.get("PSNET_DEP_CONTEXT", False):
-            droute = self.dep_context_route(depth.device)
+            droute = self._grad_stack_route("dep_context_precision", self.dep_context_route, depth.device) if diff \
+                else self.dep_context_route(depth.device)
             if droute in ("fp16", "bf16"):
                 # upsample, cat and the stack on libsfm_hip: the features in the dtype they arrive in, no float32
                 # copy, no full-resolution temporary but the stack's own

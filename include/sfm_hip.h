@@ -447,6 +447,45 @@ int sfm_plane_sweep_correlation(const float* ref, const float* tgt, int batch, i
 int sfm_depth_head(const float* cost, int batch, int nlabel, int h, int w, int H, int W, int depth_mode,
                    float min_depth, float depth_step, float* depth, void* stream);
 
+/* Backward of sfm_depth_head into the cost: the gradient autograd forms in the
+ * reference's training loop through F.interpolate(trilinear), F.softmax and
+ * disparityregression / depthregression (models/PSNet.py:194-216,
+ * models/submodule.py:57-93), whose outputs its loss reads (main.py:387-389).
+ * With v_l the forward's interpolated logit at an output pixel, p = softmax(v),
+ * val_l = (l + 1) step, reg = sum_l p_l val_l and d = grad_depth * dout/dreg
+ * (min_depth in depth mode, -(min_depth L) / (reg + 1e-16)^2 in disparity mode):
+ *   grad_cost[b, l, y, x] = sum over the output pixels whose taps include (y, x)
+ *                           of d p_l (val_l - reg) wy wx
+ * with the forward's own taps, weights and exponentials (the same bits): the
+ * exact transpose of sfm_depth_head.
+ *   cost, batch ... depth_step   exactly what the forward call was given
+ *              (min_depth is its multiplier argument)
+ *   grad_depth [dev] batch x H x W float32
+ *   grad_cost  [dev] batch x nlabel x h x w float32, every element written;
+ *              must not alias cost
+ *   workspace  [dev] sfm_depth_head_backward_workspace_bytes(batch, H, W) bytes
+ *              (24 per output pixel), 8-byte aligned; SFM_ERR_WORKSPACE with the
+ *              needed size in the message when it is missing or too small
+ * sfm_depth_head's shape limits, and nlabel <= 8 * 65535.  A gather without
+ * atomics: one thread owns an element and sums its contributors in a fixed
+ * order, so the result is reproducible bit for bit from call to call; a cell no
+ * output pixel reads (downsampling) gets exactly 0. */
+size_t sfm_depth_head_backward_workspace_bytes(int batch, int H, int W);
+int sfm_depth_head_backward(const float* cost, const float* grad_depth, int batch, int nlabel, int h, int w, int H,
+                            int W, int depth_mode, float min_depth, float depth_step, float* grad_cost,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* The transpose of the head's interpolation along one axis (host only, no
+ * device work): the output indices of F.interpolate(align_corners=False) from
+ * in_size to out_size (PSNet.py:194-197) whose taps include `cell`.
+ * [*first0, *first0 + *count0) read it as tap 0, [*first1, *first1 + *count1)
+ * as tap 1; both are contiguous runs because the source index is monotone in
+ * the output index.  Tap 1 is the cell after tap 0, or the same cell at the
+ * last index, or the output's own cell when the sizes match.  An empty run
+ * has count 0.  This is the function sfm_depth_head_backward's gather walks. */
+int sfm_depth_head_contributors(int in_size, int out_size, int cell, int* first0, int* count0, int* first1,
+                                int* count1);
+
 /* K^-1 of a batch of 3x3 matrices, as models/SFMnet.py:104 forms it
  * (intrinsic_inv_gpu = torch.inverse(intrinsic_gpu)): bit for bit what
  * torch.linalg.inv_ex returns on ROCm (rocsolver getrf + getrs order), in one

@@ -59,6 +59,7 @@ struct Tuning {
   int sweep_f16_feat = 1;        // read by the Python depth stage only (sfm_amd.regularize.sweep_regularize_fused,
                                  // sfm_amd.psnet): 1: float16 features go to the fused sweep as they come
                                  // (sfm_plane_sweep_cl_f16); 0: widened to float32 first (sfm_plane_sweep_cl)
+  int conv_wgrad_blocks = 0;     // k_conv3_wgrad accumulating blocks (1..4096); 0: by tile count, at most 512
 };
 Tuning& tuning();
 

@@ -126,6 +126,11 @@ _SIGS = [
     ("sfm_conv3_f16", ctypes.c_int,
      [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_dp,
       ctypes.c_int, ctypes.c_int, _c_dp, _c_dp]),
+    ("sfm_conv3_wgrad_f16_workspace_bytes", ctypes.c_size_t,
+     [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    ("sfm_conv3_wgrad_f16", ctypes.c_int,
+     [_c_dp, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp,
+      ctypes.c_size_t, _c_dp]),
     ("sfm_to_channels_last_f16", ctypes.c_int,
      [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _c_dp, _c_dp]),
     ("sfm_conv3_f32", ctypes.c_int,

@@ -20,6 +20,8 @@ and runs its forward with the hot path on libsfm_hip:
   training            grad mode on, features that require grad:        sfm_plane_sweep_ex / _backward and
                       the sweep and both heads with a backward,        sfm_depth_head / _backward (HIP);
                       the stacks as the nn.Modules they are            torch (MIOpen)
+                      dres0..4 / classify under float16 autocast       sfm_conv3_f16 / sfm_conv3_wgrad_f16 (HIP MFMA)
+                      with ``regularize_grad`` "fp16"                   between torch's BatchNorm3d
   dep_convs           full-resolution depth refinement (PSNET_DEP_CONTEXT, 218-225): bilinear upsample + cat
                       sfm_dep_context_pack_* (HIP), the stack      sfm_conv2_* (HIP MFMA) under float16 autocast
                       in eval mode (``dep_context_precision``); else   torch (MIOpen)
@@ -49,6 +51,11 @@ FEATURE_AUTO_HIP = True
 # Whether the differentiable route's heads are depth_head_autograd (sfm_depth_head + sfm_depth_head_backward) or
 # torch_depth_head: the same-process A/B of scripts/depth_head_bwd_ab.py decides it (profiles/depth_head_bwd_ab.txt)
 HEAD_BWD_HIP = True
+
+# Whether regularize_grad="auto" may resolve to "fp16" (CostRegularization.forward_differentiable: sfm_conv3_f16 and
+# sfm_conv3_wgrad_f16) on the differentiable route under float16 autocast, or stays with the nn.Modules: the
+# same-process A/B of scripts/stack_bwd_ab.py decides it (profiles/stack_bwd_ab.txt)
+STACK_BWD_HIP = True
 
 
 def torch_depth_head(cost, nlabel, min_depth, out_hw, predict_by_depth=False, scale=None):
@@ -195,13 +202,22 @@ class PSNet(CostRegularization):
     bits of ``depth_head``).  ``conv_precision`` and ``cost_dtype`` apply to
     the forward-only route alone; a forced "fp16" / "bf16" context,
     dep-context or feature precision has no backward and raises there.
+    ``regularize_grad`` selects how that route runs ``dres0..4`` and
+    ``classify``: "torch" (the modules), "fp16"
+    (``CostRegularization.forward_differentiable``: every Conv3d forward and
+    backward on libsfm_hip in float16, BatchNorm3d as the module it is; needs
+    float16 CUDA autocast at the call and raises without it) or "auto"
+    (default): "fp16" exactly where the modules would compute in float16
+    anyway -- a CUDA device, float16 autocast active at the call -- the stacks
+    are the stock modules without forward (pre-)hooks, and STACK_BWD_HIP is on;
+    "torch" everywhere else.
     Everything else is unchanged bit for bit: calls under ``torch.no_grad()``
     in either mode, and the float16 eval routes, whose HIP features carry no
     grad and so never enter the differentiable route."""
 
     def __init__(self, nlabel, mindepth=None, cfg=None, feature_fn=None, cost_dtype=torch.float32,
                  conv_precision="auto", context_precision="auto", dep_context_precision="auto",
-                 feature_precision="auto"):
+                 feature_precision="auto", regularize_grad="auto"):
         super().__init__(64)
         c = _default_cfg if cfg is None else cfg
         if c.get("COST_BY_COLOR", False) or c.get("COST_BY_COLOR_WITH_FEAT", False):
@@ -224,6 +240,9 @@ class PSNet(CostRegularization):
         if feature_precision not in ("auto", "torch", "fp16"):
             raise ValueError(f"unknown feature precision {feature_precision!r}")
         self.feature_precision = feature_precision
+        if regularize_grad not in ("auto", "torch", "fp16"):
+            raise ValueError(f"unknown regularize_grad {regularize_grad!r}")
+        self.regularize_grad = regularize_grad
         self.feature_extraction = FeatureExtraction() if feature_fn is None else feature_fn
         if c.get("IND_CONTEXT", False):
             self.context_net = FeatureExtraction()
@@ -303,6 +322,43 @@ class PSNet(CostRegularization):
                                f"run under torch.no_grad(), or leave {arg} at 'auto' or 'torch'")
         return "torch"
 
+    def _stock_regularizer(self):
+        """dres0..4 and classify are the stock modules and nothing else runs when they are called: the layout
+        ``layer_plan`` reads, no forward (pre-)hooks on the blocks or anything inside them."""
+        plan_mods = set()
+        try:
+            for conv, bn, _, _ in self.layer_plan():
+                if type(conv) is not nn.Conv3d or conv.bias is not None or (bn is not None and
+                                                                            type(bn) is not nn.BatchNorm3d):
+                    return False
+                plan_mods.add(conv)
+                plan_mods.add(bn)
+        except (AttributeError, IndexError, TypeError):
+            return False
+        for name in ("dres0", "dres1", "dres2", "dres3", "dres4", "classify"):
+            for m in getattr(self, name).modules():
+                if m._forward_hooks or m._forward_pre_hooks:
+                    return False
+                if not isinstance(m, (nn.Sequential, nn.ReLU)) and m not in plan_mods:
+                    return False
+        return True
+
+    def regularize_grad_route(self, device=None):
+        """How the differentiable route runs dres0..4 and classify at this
+        call: "torch" or "fp16" (see ``regularize_grad``)."""
+        p = self.regularize_grad
+        if p == "torch":
+            return p
+        on_gpu = device is not None and torch.device(device).type == "cuda"
+        half = on_gpu and torch.is_autocast_enabled() and _autocast_gpu_dtype() == torch.float16
+        if p == "fp16":
+            if not half:
+                raise RuntimeError("regularize_grad='fp16' computes the stack in float16 on the GPU: call the model "
+                                   "on a CUDA device under torch.autocast('cuda', torch.float16), or leave "
+                                   "regularize_grad at 'auto' or 'torch'")
+            return p
+        return "fp16" if half and STACK_BWD_HIP and self._stock_regularizer() else "torch"
+
     def _regularize_modules(self, cost):
         """dres0..4 and classify as PSNet.py:160-165 calls them: the modules themselves, which carry a gradient
         and whose BatchNorm follows self.training (the matrix-core stack folds it and has no backward)."""
@@ -342,7 +398,10 @@ class PSNet(CostRegularization):
                 ref_fea = ref_raw.float() if ref_fea is None else ref_fea
                 cost = plane_sweep_cost_autograd(ref_fea, tgt_raw.float(), pose[:, j].float(), K4, Ki4, self.nlabel,
                                                  self.mindepth, predict_by_depth=pbd)
-                c0 = self._regularize_modules(cost)
+                if self.regularize_grad_route(cost.device) == "fp16":
+                    c0 = self.forward_differentiable(cost)
+                else:
+                    c0 = self._regularize_modules(cost)
                 costs = c0 if costs is None else costs + c0
                 continue
             if fused and f16_features(ref_raw, tgt_raw):

@@ -116,6 +116,116 @@ def conv3_f16(x, weights, scale, bias, residual=None, relu=False, cout=32):
     return _conv3_lp(x, weights, scale, bias, residual, relu, cout, torch.float16)
 
 
+def pack_weights(weight):
+    """A Conv3d weight [cout, cin, 3, 3, 3] in sfm_conv3_*'s pack layout:
+    [27, 32, cin], tap = (kd*3 + kh)*3 + kw, cout zero-padded to 32.  Pure
+    torch, any device and dtype."""
+    cout, cin = weight.shape[:2]
+    wp = weight.new_zeros(27, 32, cin)
+    wp[:, :cout] = weight.permute(2, 3, 4, 0, 1).reshape(27, cout, cin)
+    return wp
+
+
+def pack_dgrad_weights(weight):
+    """The weights that turn sfm_conv3_f16 into the layer's data gradient
+    (sfm_hip.h): Wd[half][t][ci][co] = W[co][32 half + ci][26 - t] as
+    [cin / 32, 27, 32, 32], co zero-padded to 32 -- one pack per 32-channel
+    half of ci, each an ordinary 32 -> 32 layer on the output gradient.  Pure
+    torch, any device and dtype."""
+    cout, cin = weight.shape[:2]
+    flipped = weight.reshape(cout, cin, 27).flip(2)                  # [co][ci][t] = W[co][ci][26 - t]
+    wd = weight.new_zeros(cin // 32, 27, 32, 32)
+    wd[..., :cout] = flipped.permute(2, 1, 0).reshape(27, cin // 32, 32, cout).permute(1, 0, 2, 3)
+    return wd
+
+
+def unpack_wgrad(gwp, cout, cin):
+    """sfm_conv3_wgrad_f16's [27, 32, cin] result in the Conv3d parameter's
+    layout [cout, cin, 3, 3, 3] (rows co >= cout belong to the padding and are
+    dropped).  Pure torch."""
+    return gwp[:, :cout].permute(1, 2, 0).reshape(cout, cin, 3, 3, 3).contiguous()
+
+
+def conv3_wgrad_f16(x, grad_out):
+    """sfm_conv3_wgrad_f16: x [B, L, h, w, cin] and grad_out [B, L, h, w, 32],
+    contiguous float16 device tensors -> [27, 32, cin] float32, reproducible
+    bit for bit."""
+    for t, n in ((x, "x"), (grad_out, "grad_out")):
+        if not (t.is_cuda and t.dtype == torch.float16 and t.is_contiguous() and t.dim() == 5):
+            raise RuntimeError(f"{n} must be a contiguous 5-D float16 device tensor")
+    B, L, h, w, cin = x.shape
+    if tuple(grad_out.shape) != (B, L, h, w, 32):
+        raise RuntimeError("grad_out must be [B, L, h, w, 32]")
+    lib = _lib.load()
+    gw = torch.empty((27, 32, cin), dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(1, lib.sfm_conv3_wgrad_f16_workspace_bytes(B, cin, L, h, w)), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.sfm_conv3_wgrad_f16(_lib.ptr(x), _lib.ptr(grad_out), B, cin, 32, L, h, w, _lib.ptr(gw), _lib.ptr(ws),
+                                     ws.numel(), _lib.stream_ptr(x.device))
+        _lib.check(rc, "sfm_conv3_wgrad_f16")
+    return gw
+
+
+_UNIT = {}
+
+
+def _unit_affine(device):
+    """scale 1 / bias 0 of a raw convolution, once per device."""
+    key = str(device)
+    if key not in _UNIT:
+        _UNIT[key] = (torch.ones(32, device=device), torch.zeros(32, device=device))
+    return _UNIT[key]
+
+
+class _Conv3(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight):
+        cout = int(weight.shape[0])
+        one, zero = _unit_affine(x.device)
+        y = conv3_f16(x, pack_weights(weight.detach().float()).half().contiguous(), one, zero, None, False, cout)
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, weight = ctx.saved_tensors
+        cout, cin = int(weight.shape[0]), int(weight.shape[1])
+        if cout == 32:
+            gp = g.to(torch.float16).contiguous()
+        else:
+            # classify's 32 -> 1 layer: its gradient as channel 0 of a zero-padded 32-channel tensor
+            gp = torch.zeros(tuple(g.shape) + (32,), dtype=torch.float16, device=g.device)
+            gp[..., 0] = g
+        grad_x = grad_w = None
+        if ctx.needs_input_grad[0]:
+            one, zero = _unit_affine(x.device)
+            wd = pack_dgrad_weights(weight.detach().float()).half().contiguous()
+            parts = [conv3_f16(gp, wd[k], one, zero, None, False, 32) for k in range(cin // 32)]
+            grad_x = parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
+        if ctx.needs_input_grad[1]:
+            grad_w = unpack_wgrad(conv3_wgrad_f16(x, gp), cout, cin).to(weight.dtype)
+        return grad_x, grad_w
+
+
+def conv3_autograd(x, weight):
+    """One raw 3x3x3 Conv3d of the stack with a backward on libsfm_hip: x
+    [B, L, h, w, cin] float16 on the device (channels-last), ``weight`` the
+    module's float32 parameter [cout, cin, 3, 3, 3] (rounded to float16 as
+    autocast rounds it) -> sfm_conv3_f16's output with scale 1, bias 0, no
+    ReLU and no residual, bit for bit: [B, L, h, w, 32] float16, or
+    [B, L, h, w] float32 for cout 1.  Backward: the data gradient is
+    sfm_conv3_f16 on ``pack_dgrad_weights``' weights, the weight gradient
+    sfm_conv3_wgrad_f16, returned as float32 in the parameter's layout; each
+    only when its input needs a gradient."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float16 and x.dim() == 5):
+        raise RuntimeError("conv3_autograd needs a [B, L, h, w, cin] float16 device tensor (HIP path, no CPU fallback)")
+    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or weight.shape[0] not in (1, 32) or \
+            weight.shape[1] != x.shape[-1] or weight.shape[1] not in (32, 64):
+        raise RuntimeError("weight must be [32 or 1, cin, 3, 3, 3] with cin 32 or 64, the channels of x")
+    return _Conv3.apply(x.contiguous(), weight)
+
+
 class CostRegularization(nn.Module):
     """dres0..dres4 + classify of PSNet (PSNet.py:79-102), initialised as
     PSNet.py:104-118 (Conv3d ~ N(0, sqrt(2 / (27 * out_channels))), BN = 1 / 0)."""
@@ -211,6 +321,38 @@ class CostRegularization(nn.Module):
         if C != packed[0]["cin"]:
             raise RuntimeError(f"cost has {C} channels, the first layer expects {packed[0]['cin']}")
         return self.forward_channels_last(to_channels_last(cost, _ACT_DTYPE[precision]), precision=precision)
+
+    def forward_differentiable(self, cost):
+        """The stack of PSNet.py:160-165 with a backward in float16 on
+        libsfm_hip: cost [B, Cin, L, h, w] float32 on the device -> [B, 1, L,
+        h, w] float32.  Every Conv3d is ``conv3_autograd`` (sfm_conv3_f16
+        forward and data gradient, sfm_conv3_wgrad_f16) on channels-last
+        float16 activations; every BatchNorm3d is called as the module it is,
+        on the channels-last tensor viewed as [B, 32, L, h, w], so batch
+        statistics in training mode, the running-stat updates, eval mode and a
+        loaded state_dict are torch's; ReLU and the residual adds are torch
+        ops.  The precision is that of the modules under float16 autocast."""
+        if not (isinstance(cost, torch.Tensor) and cost.is_cuda):
+            raise RuntimeError("CostRegularization.forward_differentiable needs a device tensor (HIP path, no CPU "
+                               "fallback)")
+        if cost.dim() != 5 or cost.shape[1] != self.dres0[0][0].in_channels:
+            raise RuntimeError(f"cost must be [B, {self.dres0[0][0].in_channels}, L, h, w]")
+        x = cost.permute(0, 2, 3, 4, 1).to(torch.float16).contiguous()        # [B, L, h, w, Cin]
+        keep = None
+        for li, (conv, bn, relu, resid) in enumerate(self.layer_plan()):
+            y = conv3_autograd(x, conv.weight)
+            if bn is None:
+                return y.unsqueeze(1)                                          # classify's last layer: [B, L, h, w] fp32
+            y = bn(y.permute(0, 4, 1, 2, 3))                                   # a [B, 32, L, h, w] view, channels last
+            if relu:
+                y = torch.relu(y)
+            y = y.permute(0, 2, 3, 4, 1)
+            if resid:
+                y = y + keep
+            x = y.to(torch.float16).contiguous()
+            if li == 1 or resid:
+                keep = x
+        raise AssertionError("layer_plan ends with classify's plain convolution")
 
     def forward_channels_last(self, x, precision="fp32x3"):
         """``forward`` on the channels-last volume: x [B, L, h, w, Cin],

@@ -592,6 +592,45 @@ int sfm_conv3_f16(const void* in, int batch, int cin, int depth, int h, int w, c
 int sfm_to_channels_last_f16(const void* in, int in_dtype, int batch, int channels, int64_t plane, void* out,
                              void* stream);
 
+/* Training the same layers in float16 (the reference trains under float16
+ * autocast, cfgs/kitti.yml:10 MIXED_PREC): the weight gradient of one raw
+ * Conv3d of the stack (models/PSNet.py:79-102, applied at PSNet.py:159-165),
+ * on v_mfma_f32_32x32x16_f16 with fp32 accumulation:
+ *   grad_weights[tap][co][ci] = sum over b, p of grad_out[b, p, co] in[b, p + tap - 1, ci]
+ * (p + tap - 1 per axis, zero outside the volume; tap = (kd*3 + kh)*3 + kw).
+ *   in           [dev] batch x depth x h x w x cin float16, cin 32 or 64: the
+ *                layer's input, as sfm_conv3_f16 read it;
+ *   grad_out     [dev] batch x depth x h x w x 32 float16: the gradient of the raw
+ *                convolution's output.  cout must be 32: a cout 1 layer
+ *                (classify's last) passes its gradient as channel 0 of a
+ *                zero-padded 32-channel tensor and reads row co = 0;
+ *   grad_weights [dev] 27 x 32 x cin float32, sfm_conv3_f16's pack layout;
+ *   workspace    [dev] sfm_conv3_wgrad_f16_workspace_bytes(batch, cin, depth, h, w)
+ *                bytes, 16-byte aligned: one 27 x 32 x 32 float32 partial sum per
+ *                accumulating block and 32-channel half of cin.
+ * Every pointer 16-byte aligned; grad_weights and workspace overlap neither
+ * each other nor an input.  A fixed grid of accumulating blocks walks the
+ * volume and a second launch adds their partial sums in block order: no float
+ * atomics, so the result is reproducible bit for bit from run to run.  The
+ * number of blocks is min(tiles, 512) (a tile: one plane, 4 rows, 64 columns),
+ * or the tuning key conv_wgrad_blocks (1..4096; 0, default: as above) -- launch
+ * shape only, read by both functions, and like sweep_fused_cl taken by
+ * sfm_tune_set / sfm_tune_get without being enumerated by sfm_tune_key: it is
+ * the tests' handle on few blocks, many blocks and more blocks than tiles.
+ * Profile name "conv3_wgrad".
+ *
+ * The data gradient needs no kernel of its own.  With W[co][ci][tap] the
+ * layer's weights,
+ *   grad_in[p, ci] = sum over tap, co of W[co][ci][tap] grad_out[p - (tap - 1), co]
+ * is sfm_conv3_f16 (scale 1, bias 0, relu 0, no residual, cout 32) on
+ * grad_out with the flipped, transposed weights Wd[t][ci][co] = W[co][ci][26 - t]
+ * as its 27 x 32 x 32 `weights`: one call for cin 32; for cin 64 one call per
+ * 32-channel half of ci, the two outputs joined along the channel axis; for
+ * cout 1, grad_out zero-padded to 32 channels as above. */
+size_t sfm_conv3_wgrad_f16_workspace_bytes(int batch, int cin, int depth, int h, int w);
+int sfm_conv3_wgrad_f16(const void* in, const void* grad_out, int batch, int cin, int cout, int depth, int h, int w,
+                        float* grad_weights, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The same layer at the reference's precision (conv_precision "fp32"):
  * float32 operands on v_mfma_f32_32x32x2_f32 (an exact fmaf chain: products
  * and sums round as float32 arithmetic; only the summation order differs from

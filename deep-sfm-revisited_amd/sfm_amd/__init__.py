@@ -6,7 +6,8 @@ libsfm_hip.so (include/sfm_hip.h):
   sweep    plane-sweep cost volume (planar, or channels-last for the regulariser), inverse_warp,
            PSNet sweep section; plane_sweep_cost_autograd / inverse_warp_autograd with a gradient into the features
   regularize  PSNet 3-D cost regularisation (dres0..classify) on the matrix cores; conv3_autograd with a float16
-           backward (data and weight gradient) for training
+           backward (data and weight gradient) for training, batchnorm3_act_autograd (BatchNorm3d + ReLU + residual
+           in float16, forward and backward)
   depth    correlation cost and the soft-argmin depth head; depth_head_autograd with a gradient into the cost
   synth    seeded synthetic KITTI-shaped inputs
   dist     one-process-per-GPU pair sharding and RCCL metric gather
@@ -15,7 +16,7 @@ libsfm_hip.so (include/sfm_hip.h):
 from . import _lib  # noqa: F401
 
 __all__ = ["ransac", "sweep", "regularize", "synth", "dist", "config", "validate", "plane_sweep_cost_autograd",
-           "inverse_warp_autograd", "depth_head_autograd", "conv3_autograd"]
+           "inverse_warp_autograd", "depth_head_autograd", "conv3_autograd", "batchnorm3_act_autograd"]
 
 
 def __getattr__(name):
@@ -26,7 +27,7 @@ def __getattr__(name):
     if name == "depth_head_autograd":
         from . import depth
         return depth.depth_head_autograd
-    if name == "conv3_autograd":
+    if name in ("conv3_autograd", "batchnorm3_act_autograd"):
         from . import regularize
-        return regularize.conv3_autograd
+        return getattr(regularize, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -21,7 +21,8 @@ and runs its forward with the hot path on libsfm_hip:
                       the sweep and both heads with a backward,        sfm_depth_head / _backward (HIP);
                       the stacks as the nn.Modules they are            torch (MIOpen)
                       dres0..4 / classify under float16 autocast       sfm_conv3_f16 / sfm_conv3_wgrad_f16 (HIP MFMA)
-                      with ``regularize_grad`` "fp16"                   between torch's BatchNorm3d
+                      with ``regularize_grad`` "fp16"                   between torch's BatchNorm3d, or with
+                      ``regularize_norm`` "hip"                        sfm_bn3_stats / _apply / _backward_f16 (HIP)
   dep_convs           full-resolution depth refinement (PSNET_DEP_CONTEXT, 218-225): bilinear upsample + cat
                       sfm_dep_context_pack_* (HIP), the stack      sfm_conv2_* (HIP MFMA) under float16 autocast
                       in eval mode (``dep_context_precision``); else   torch (MIOpen)
@@ -210,14 +211,18 @@ class PSNet(CostRegularization):
     (default): "fp16" exactly where the modules would compute in float16
     anyway -- a CUDA device, float16 autocast active at the call -- the stacks
     are the stock modules without forward (pre-)hooks, and STACK_BWD_HIP is on;
-    "torch" everywhere else.
+    "torch" everywhere else.  ``regularize_norm`` says how the "fp16" route
+    runs the stack's BatchNorm3d, ReLU and residual adds: "torch" (default: the
+    modules and torch ops) or "hip" (opt-in: ``batchnorm3_act_autograd``,
+    sfm_bn3_* in both directions; profiles/stack_norm_ab.txt); it has no effect
+    on the "torch" route.
     Everything else is unchanged bit for bit: calls under ``torch.no_grad()``
     in either mode, and the float16 eval routes, whose HIP features carry no
     grad and so never enter the differentiable route."""
 
     def __init__(self, nlabel, mindepth=None, cfg=None, feature_fn=None, cost_dtype=torch.float32,
                  conv_precision="auto", context_precision="auto", dep_context_precision="auto",
-                 feature_precision="auto", regularize_grad="auto"):
+                 feature_precision="auto", regularize_grad="auto", regularize_norm="torch"):
         super().__init__(64)
         c = _default_cfg if cfg is None else cfg
         if c.get("COST_BY_COLOR", False) or c.get("COST_BY_COLOR_WITH_FEAT", False):
@@ -243,6 +248,9 @@ class PSNet(CostRegularization):
         if regularize_grad not in ("auto", "torch", "fp16"):
             raise ValueError(f"unknown regularize_grad {regularize_grad!r}")
         self.regularize_grad = regularize_grad
+        if regularize_norm not in ("torch", "hip"):
+            raise ValueError(f"unknown regularize_norm {regularize_norm!r}")
+        self.regularize_norm = regularize_norm
         self.feature_extraction = FeatureExtraction() if feature_fn is None else feature_fn
         if c.get("IND_CONTEXT", False):
             self.context_net = FeatureExtraction()
@@ -399,7 +407,7 @@ class PSNet(CostRegularization):
                 cost = plane_sweep_cost_autograd(ref_fea, tgt_raw.float(), pose[:, j].float(), K4, Ki4, self.nlabel,
                                                  self.mindepth, predict_by_depth=pbd)
                 if self.regularize_grad_route(cost.device) == "fp16":
-                    c0 = self.forward_differentiable(cost)
+                    c0 = self.forward_differentiable(cost, norm=self.regularize_norm)
                 else:
                     c0 = self._regularize_modules(cost)
                 costs = c0 if costs is None else costs + c0

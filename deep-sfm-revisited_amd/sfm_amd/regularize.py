@@ -226,6 +226,165 @@ def conv3_autograd(x, weight):
     return _Conv3.apply(x.contiguous(), weight)
 
 
+def _bn3_operand(t, name, like=None):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float16 and t.dim() >= 2 and
+            t.shape[-1] == 32 and t.is_contiguous()):
+        raise RuntimeError(f"{name} must be a contiguous [..., 32] float16 device tensor (HIP path, no CPU fallback)")
+    if like is not None and t.shape != like.shape:
+        raise RuntimeError(f"{name} must have the shape of x")
+
+
+def bn3_stats_f16(x, gamma, beta, eps=1e-5, running_mean=None, running_var=None, momentum=0.1, training=True):
+    """sfm_bn3_stats_f16: x [..., 32] float16 (channels last), gamma / beta and
+    the running statistics [32] float32 on x's device -> stats [5, 32] float32
+    (mean, biased variance, invstd, a, b).  In training mode the running
+    statistics, where given, are updated in place; in eval mode they are read."""
+    _bn3_operand(x, "x")
+    lib = _lib.load()
+    vox = x.numel() // 32
+    stats = torch.empty((5, 32), dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(16, lib.sfm_bn3_stats_f16_workspace_bytes(vox, 1 if training else 0)), dtype=torch.uint8,
+                     device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.sfm_bn3_stats_f16(_lib.ptr(x), vox, _lib.ptr(gamma), _lib.ptr(beta), float(eps), _lib.ptr(running_mean),
+                                   _lib.ptr(running_var), float(momentum), 1 if training else 0, _lib.ptr(stats),
+                                   _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device))
+        _lib.check(rc, "sfm_bn3_stats_f16")
+    if training:
+        for r in (running_mean, running_var):       # written through the raw pointer: tell autograd and pack()'s key
+            if r is not None:
+                torch.autograd.graph.increment_version(r)
+    return stats
+
+
+def bn3_apply_f16(x, stats, residual=None, relu=False):
+    """sfm_bn3_apply_f16: f16(relu(fma(a, x, b)) + residual) with a, b from
+    ``stats`` [5, 32] float32; x and residual [..., 32] float16."""
+    _bn3_operand(x, "x")
+    if residual is not None:
+        _bn3_operand(residual, "residual", x)
+    out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().sfm_bn3_apply_f16(_lib.ptr(x), x.numel() // 32, _lib.ptr(stats), _lib.ptr(residual),
+                                           1 if relu else 0, _lib.ptr(out), _lib.stream_ptr(x.device))
+        _lib.check(rc, "sfm_bn3_apply_f16")
+    return out
+
+
+def bn3_backward_f16(x, grad_out, stats, relu=False, training=True, need_grad_x=True):
+    """sfm_bn3_backward_f16 -> (grad_x float16 like x or None, grad_gamma_beta
+    [2, 32] float32: dgamma, dbeta), from x and ``stats`` alone."""
+    _bn3_operand(x, "x")
+    _bn3_operand(grad_out, "grad_out", x)
+    lib = _lib.load()
+    vox = x.numel() // 32
+    gx = torch.empty_like(x) if need_grad_x else None
+    ggb = torch.empty((2, 32), dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(16, lib.sfm_bn3_backward_f16_workspace_bytes(vox)), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.sfm_bn3_backward_f16(_lib.ptr(x), _lib.ptr(grad_out), vox, _lib.ptr(stats), 1 if relu else 0,
+                                      1 if training else 0, _lib.ptr(gx), _lib.ptr(ggb), _lib.ptr(ws), ws.numel(),
+                                      _lib.stream_ptr(x.device))
+        _lib.check(rc, "sfm_bn3_backward_f16")
+    return gx, ggb
+
+
+class _BN3Act(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, bn, relu):
+        training = bool(bn.training)
+        stats = bn3_stats_f16(x, weight.detach(), bias.detach(), bn.eps, bn.running_mean, bn.running_var, bn.momentum,
+                              training)
+        if training:
+            bn.num_batches_tracked.add_(1)
+        out = bn3_apply_f16(x, stats, None if residual is None else residual.detach(), relu)
+        ctx.save_for_backward(x, stats)
+        ctx.relu, ctx.training, ctx.param_dtypes = relu, training, (weight.dtype, bias.dtype)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, stats = ctx.saved_tensors
+        need_x, need_w, need_b, need_r = ctx.needs_input_grad[:4]
+        gx = gw = gb = None
+        if need_x or need_w or need_b:
+            gx, ggb = bn3_backward_f16(x, g.to(torch.float16).contiguous(), stats, ctx.relu, ctx.training, need_x)
+            gw = ggb[0].to(ctx.param_dtypes[0]) if need_w else None
+            gb = ggb[1].to(ctx.param_dtypes[1]) if need_b else None
+        return gx, gw, gb, (g if need_r else None), None, None
+
+
+def batchnorm3_act_autograd(x, bn, relu=False, residual=None):
+    """``bn`` (an nn.BatchNorm3d of 32 channels), then ReLU if ``relu``, then
+    ``+ residual``, on libsfm_hip in both directions: x and residual
+    [B, L, h, w, 32] float16 on the device, channels last -> the same shape,
+    float16, rounded once (sfm_bn3_stats_f16, sfm_bn3_apply_f16).  The module's
+    mode, eps, momentum and affine parameters are honoured: training mode takes
+    batch statistics, updates the running statistics in place by torch's rule
+    and increments num_batches_tracked; eval mode reads the running statistics.
+    Only x and the 160 floats of statistics are saved; the backward
+    (sfm_bn3_backward_f16) returns gradients for x, bn.weight, bn.bias and the
+    residual (the output gradient itself), each only where needed.  A module
+    that is not the stock affine one with running statistics and a fixed
+    momentum, or that carries forward hooks, raises; so does a CPU tensor."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float16 and x.dim() == 5 and
+            x.shape[-1] == 32):
+        raise RuntimeError("batchnorm3_act_autograd needs a [B, L, h, w, 32] float16 device tensor (HIP path, no CPU "
+                           "fallback)")
+    if type(bn) is not nn.BatchNorm3d or bn.num_features != 32:
+        raise RuntimeError("bn must be an nn.BatchNorm3d of 32 channels")
+    if not bn.affine or not bn.track_running_stats or bn.momentum is None or bn.running_mean is None:
+        raise RuntimeError("bn must be the stock module: affine=True, track_running_stats=True and a fixed momentum")
+    if bn._forward_hooks or bn._forward_pre_hooks:
+        raise RuntimeError("bn carries forward hooks, which the HIP route would not call")
+    for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var):
+        if not (t.device == x.device and t.dtype == torch.float32 and t.is_contiguous()):
+            raise RuntimeError("bn's parameters and running statistics must be float32 on x's device")
+    if x.numel() // 32 < 2 and bn.training:
+        raise RuntimeError("training-mode batch statistics need more than one value per channel")
+    if residual is not None and not (isinstance(residual, torch.Tensor) and residual.is_cuda and
+                                     residual.dtype == torch.float16 and residual.shape == x.shape):
+        raise RuntimeError("residual must be a float16 device tensor of x's shape")
+    return _BN3Act.apply(x.contiguous(), bn.weight, bn.bias, None if residual is None else residual.contiguous(), bn,
+                         bool(relu))
+
+
+def bn3_act_reference(x, gamma, beta, running_mean=None, running_var=None, training=True, momentum=0.1, eps=1e-5,
+                      relu=False, residual=None):
+    """The mathematics of ``batchnorm3_act_autograd`` in torch ops in float64,
+    on any device (tests and documents only): x [..., C] channels last ->
+    (out, new running_mean, new running_var), all float64; differentiable by
+    autograd in x, gamma, beta and residual.  Training mode: batch mean and
+    biased variance, the running statistics moved by (1 - momentum) r +
+    momentum batch with the unbiased variance; eval mode: the running
+    statistics, returned as they came."""
+    x = x.double()
+    gamma, beta = gamma.double(), beta.double()
+    flat = x.reshape(-1, x.shape[-1])
+    n = flat.shape[0]
+    if training:
+        mean = flat.mean(0)
+        var = ((flat - mean) ** 2).mean(0)
+        new_mean = new_var = None
+        if running_mean is not None:
+            new_mean = (1.0 - momentum) * running_mean.double() + momentum * mean.detach()
+        if running_var is not None:
+            new_var = (1.0 - momentum) * running_var.double() + momentum * var.detach() * n / (n - 1)
+    else:
+        mean, var = running_mean.double(), running_var.double()
+        new_mean, new_var = mean, var
+    invstd = 1.0 / torch.sqrt(var + eps)
+    a = gamma * invstd
+    b = beta - mean * a
+    z = a * x + b
+    if relu:
+        z = torch.relu(z)
+    if residual is not None:
+        z = z + residual.double()
+    return z, new_mean, new_var
+
+
 class CostRegularization(nn.Module):
     """dres0..dres4 + classify of PSNet (PSNet.py:79-102), initialised as
     PSNet.py:104-118 (Conv3d ~ N(0, sqrt(2 / (27 * out_channels))), BN = 1 / 0)."""
@@ -322,7 +481,7 @@ class CostRegularization(nn.Module):
             raise RuntimeError(f"cost has {C} channels, the first layer expects {packed[0]['cin']}")
         return self.forward_channels_last(to_channels_last(cost, _ACT_DTYPE[precision]), precision=precision)
 
-    def forward_differentiable(self, cost):
+    def forward_differentiable(self, cost, norm="torch"):
         """The stack of PSNet.py:160-165 with a backward in float16 on
         libsfm_hip: cost [B, Cin, L, h, w] float32 on the device -> [B, 1, L,
         h, w] float32.  Every Conv3d is ``conv3_autograd`` (sfm_conv3_f16
@@ -331,7 +490,15 @@ class CostRegularization(nn.Module):
         on the channels-last tensor viewed as [B, 32, L, h, w], so batch
         statistics in training mode, the running-stat updates, eval mode and a
         loaded state_dict are torch's; ReLU and the residual adds are torch
-        ops.  The precision is that of the modules under float16 autocast."""
+        ops.  The precision is that of the modules under float16 autocast.
+        ``norm="hip"`` (opt-in) runs each BatchNorm3d with its ReLU and
+        residual add as ``batchnorm3_act_autograd`` instead (sfm_bn3_stats_f16,
+        sfm_bn3_apply_f16, sfm_bn3_backward_f16): the same module state read
+        and updated, one rounding per layer instead of two, only the
+        convolution's output and 160 floats saved; ``norm="torch"`` (default)
+        is the route above, unchanged bit for bit."""
+        if norm not in ("torch", "hip"):
+            raise ValueError(f"unknown norm {norm!r}")
         if not (isinstance(cost, torch.Tensor) and cost.is_cuda):
             raise RuntimeError("CostRegularization.forward_differentiable needs a device tensor (HIP path, no CPU "
                                "fallback)")
@@ -343,6 +510,11 @@ class CostRegularization(nn.Module):
             y = conv3_autograd(x, conv.weight)
             if bn is None:
                 return y.unsqueeze(1)                                          # classify's last layer: [B, L, h, w] fp32
+            if norm == "hip":
+                x = batchnorm3_act_autograd(y, bn, relu, keep if resid else None)
+                if li == 1 or resid:
+                    keep = x
+                continue
             y = bn(y.permute(0, 4, 1, 2, 3))                                   # a [B, 32, L, h, w] view, channels last
             if relu:
                 y = torch.relu(y)

@@ -631,6 +631,68 @@ size_t sfm_conv3_wgrad_f16_workspace_bytes(int batch, int cin, int depth, int h,
 int sfm_conv3_wgrad_f16(const void* in, const void* grad_out, int batch, int cin, int cout, int depth, int h, int w,
                         float* grad_weights, void* workspace, size_t workspace_bytes, void* stream);
 
+/* What stands between two such layers in a training step: the BatchNorm3d of
+ * convbn_3d (models/submodule.py:17-20), the ReLU and the residual add of the
+ * stack (models/PSNet.py:79-102, applied at 159-165), in float16, forward and
+ * backward.  x is the raw convolution's output, voxels x 32 float16 channels
+ * last (voxels = batch x depth x h x w, an int64_t: every offset is 64-bit).
+ * Every pointer is 16-byte aligned and no output overlaps an input.  Nothing
+ * is allocated; all launches go to `stream`.
+ *
+ * sfm_bn3_stats_f16 writes stats [dev] 5 x 32 float32: mean, biased variance,
+ * invstd = 1 / sqrt(var + eps), a = gamma invstd, b = beta - mean a.
+ *   gamma, beta  [dev] 32 float32: the module's weight and bias;
+ *   training 1:  one pass over x: sum x and sum x^2 per channel in float64 (the
+ *                product of two float16 values is exact there) by a fixed grid
+ *                of blocks, each over a contiguous voxel range, each writing one
+ *                2 x 32 double partial into `workspace`
+ *                (sfm_bn3_stats_f16_workspace_bytes(voxels, 1) bytes); a second
+ *                launch adds the partials in block order and derives the five
+ *                rows in float64, each rounded once to float32.  No atomics: two
+ *                calls give the same bits.  running_mean / running_var [dev] 32
+ *                float32, each NULL or updated in place by torch's rule,
+ *                (1 - momentum) r + momentum batch with the unbiased variance
+ *                var voxels / (voxels - 1).  voxels >= 2;
+ *   training 0:  no pass over x (which is not read), no workspace: the rows come
+ *                from running_mean / running_var, which are required and left
+ *                untouched.
+ * The number of reducing blocks is min(ceil(voxels / 128), 512), or the tuning
+ * key bn_blocks (1..4096; 0, default: as above) -- launch shape only, read by
+ * the workspace queries too, and like conv_wgrad_blocks taken by sfm_tune_set /
+ * sfm_tune_get without being enumerated by sfm_tune_key: the tests' handle on
+ * one block, few blocks and more blocks than voxels.  Profile name "bn3_stats". */
+size_t sfm_bn3_stats_f16_workspace_bytes(int64_t voxels, int training);
+int sfm_bn3_stats_f16(const void* x, int64_t voxels, const float* gamma, const float* beta, double eps,
+                      float* running_mean, float* running_var, double momentum, int training, float* stats,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* The normalisation, activation and residual add of one layer of the same
+ * stack (models/submodule.py:17-20; models/PSNet.py:79-102, 159-165) in one
+ * pass: out = f16(relu(fma(a, x, b)) + residual), a and b rows 3 and 4 of
+ * `stats`, the ReLU only with relu = 1, residual [dev] like x or NULL.  The
+ * arithmetic is float32 and the result is rounded once (the modules round
+ * after the BatchNorm and again after the add).  Profile name "bn3_apply". */
+int sfm_bn3_apply_f16(const void* x, int64_t voxels, const float* stats, const void* residual, int relu, void* out,
+                      void* stream);
+
+/* The backward of sfm_bn3_apply_f16 on sfm_bn3_stats_f16's statistics (the
+ * gradient of models/submodule.py:17-20 with the ReLU of models/PSNet.py:79-102,
+ * 159-165), from x and `stats` alone: no output and no mask is saved.
+ *   dy = grad_out, or with relu = 1 grad_out where the recomputed fma(a, x, b) > 0
+ *   (the forward's float32 expression, hence the forward's mask);
+ *   grad_gamma_beta [dev] 2 x 32 float32: dgamma = (sum dy x - mean sum dy) invstd,
+ *   then dbeta = sum dy, the sums in float64 by the grid of sfm_bn3_stats_f16,
+ *   partials in `workspace` (sfm_bn3_backward_f16_workspace_bytes(voxels) bytes)
+ *   added in block order;
+ *   grad_x [dev] like x, or NULL for the parameter gradients alone:
+ *   training 1: a (dy - dbeta / N - xhat dgamma / N), xhat = (x - mean) invstd,
+ *   N = voxels >= 2; training 0: a dy.  float32, rounded once.
+ * Two launches, no atomics: two calls give the same bits.  The residual's
+ * gradient is grad_out itself.  Profile name "bn3_bwd". */
+size_t sfm_bn3_backward_f16_workspace_bytes(int64_t voxels);
+int sfm_bn3_backward_f16(const void* x, const void* grad_out, int64_t voxels, const float* stats, int relu, int training,
+                         void* grad_x, float* grad_gamma_beta, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The same layer at the reference's precision (conv_precision "fp32"):
  * float32 operands on v_mfma_f32_32x32x2_f32 (an exact fmaf chain: products
  * and sums round as float32 arithmetic; only the summation order differs from

@@ -140,14 +140,15 @@ const TuneKey kTuneKeys[] = {
 // enumerate: the enumerated set is the launch-shape and scoring knobs the
 // header's "Tuning knobs" block documents one for one (tests/test_abi.py),
 // and these select which call writes an output, not how a kernel runs
-// (conv_wgrad_blocks, documented with sfm_conv3_wgrad_f16, and bn_blocks,
-// documented with sfm_bn3_stats_f16, are the tests' handles on those kernels'
-// grids).
+// (conv_wgrad_blocks, documented with sfm_conv3_wgrad_f16, conv2_wgrad_blocks,
+// documented with sfm_conv2_wgrad_f16, and bn_blocks, documented with
+// sfm_bn3_stats_f16, are the tests' handles on those kernels' grids).
 const TuneKey kSwitchKeys[] = {
     {"score_ref_rider", &sfm::Tuning::score_ref_rider, v_01},
     {"sweep_fused_cl", &sfm::Tuning::sweep_fused_cl, v_01},
     {"sweep_f16_feat", &sfm::Tuning::sweep_f16_feat, v_01},
     {"conv_wgrad_blocks", &sfm::Tuning::conv_wgrad_blocks, [](int v) { return v >= 0 && v <= 4096; }},
+    {"conv2_wgrad_blocks", &sfm::Tuning::conv2_wgrad_blocks, [](int v) { return v >= 0 && v <= 4096; }},
     {"bn_blocks", &sfm::Tuning::bn_blocks, [](int v) { return v >= 0 && v <= 4096; }},
 };
 const TuneKey* find_key(const char* key) {

@@ -60,6 +60,7 @@ struct Tuning {
                                  // sfm_amd.psnet): 1: float16 features go to the fused sweep as they come
                                  // (sfm_plane_sweep_cl_f16); 0: widened to float32 first (sfm_plane_sweep_cl)
   int conv_wgrad_blocks = 0;     // k_conv3_wgrad accumulating blocks (1..4096); 0: by tile count, at most 512
+  int conv2_wgrad_blocks = 0;    // k_conv2_wgrad accumulating blocks (1..4096); 0: by tile count, at most 512
   int bn_blocks = 0;             // k_bn3_stats / k_bn3_bwd_reduce reducing blocks (1..4096); 0: by voxel count, at most 512
 };
 Tuning& tuning();

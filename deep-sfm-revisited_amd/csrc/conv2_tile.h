@@ -92,9 +92,47 @@ __device__ __forceinline__ void conv2_store16(const f32x16 (&acc)[NG][PB], const
   }
 }
 
+// The data-gradient epilogue (MASK): out[p, c] = act[p, c] > 0 ? 16-bit(acc) : +0,
+// act the 16-bit activation the gradient passes the ReLU of (the output's
+// layout; null: no mask).  A select, so a non-finite accumulator under a zero
+// activation gives 0 and one under a positive activation comes through.
+template <typename A, int NG, int PB>
+__device__ __forceinline__ void conv2_store_mask(const f32x16 (&acc)[NG][PB], const unsigned short* __restrict__ act,
+                                                 unsigned short* __restrict__ out, int cout, int img, int y0, int x,
+                                                 int h, int H, int W) {
+#pragma unroll
+  for (int o = 0; o < PB; ++o) {
+    const int y = y0 + o;
+    if (y >= H) break;
+    const int64_t pix = ((int64_t)img * H + y) * W + x;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int co = 32 * g + 8 * q + 4 * h;
+        unsigned short v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = A::from_f(acc[g][o][4 * q + j]);
+        if (act) {
+          const uint2 av = *reinterpret_cast<const uint2*>(act + pix * cout + co);
+          const unsigned short a[4] = {(unsigned short)(av.x & 0xffffu), (unsigned short)(av.x >> 16),
+                                       (unsigned short)(av.y & 0xffffu), (unsigned short)(av.y >> 16)};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] = A::to_f(a[j]) > 0.0f ? v[j] : (unsigned short)0;
+        }
+        uint2 st;
+        st.x = (unsigned)v[0] | ((unsigned)v[1] << 16);
+        st.y = (unsigned)v[2] | ((unsigned)v[3] << 16);
+        *reinterpret_cast<uint2*>(out + pix * cout + co) = st;
+      }
+    }
+  }
+}
+
 // res: with RES16 the 16-bit residual of the 16-bit output (or null); without,
-// the fp32 residual of the cout 1 form (or null).
-template <bool F16, int NG, bool RES16>
+// the fp32 residual of the cout 1 form (or null); with MASK the 16-bit
+// activation of conv2_store_mask (or null), scale / bias / relu unread.
+template <bool F16, int NG, bool RES16, bool MASK = false>
 __global__ __launch_bounds__(kThreads, 2) void k_conv2(
     const unsigned short* __restrict__ in, int cin, const unsigned short* __restrict__ wpk,
     const float* __restrict__ scale, const float* __restrict__ bias, int relu, const void* __restrict__ res,
@@ -217,6 +255,10 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv2(
 
   const int x = x0 + wcol + r;
   if (x >= W) return;
+  if constexpr (MASK) {
+    conv2_store_mask<A, NG, PB>(acc, reinterpret_cast<const unsigned short*>(res), out, cout, img, y0 + wrow, x, h, H, W);
+    return;
+  }
   if (!RES16 && out1) {  // cout == 1: the 16-bit rounding torch's autocast output has, then the fp32 "+ plane"
     const float* res1 = reinterpret_cast<const float*>(res);
 #pragma unroll
@@ -238,13 +280,13 @@ __global__ __launch_bounds__(kThreads, 2) void k_conv2(
                                   out, cout, img, y0 + wrow, x, h, H, W);
 }
 
-template <bool F16, int NG, bool RES16>
+template <bool F16, int NG, bool RES16, bool MASK = false>
 void launch_conv2(hipStream_t s, const void* in, int images, int cin, int h, int w, const void* weights, int cout,
                   int dilation, const float* scale, const float* bias, int relu, const void* residual, void* out) {
   constexpr int R = rows_of(NG);
   const int ntx = (w + kTileX - 1) / kTileX, nty = (h + R - 1) / R;
   const unsigned lds = (unsigned)(w_bytes(NG) + in_bytes(NG, dilation));
-  hipLaunchKernelGGL((k_conv2<F16, NG, RES16>), dim3((unsigned)(ntx * nty * images)), dim3(kThreads), lds, s,
+  hipLaunchKernelGGL((k_conv2<F16, NG, RES16, MASK>), dim3((unsigned)(ntx * nty * images)), dim3(kThreads), lds, s,
                      (const unsigned short*)in, cin, (const unsigned short*)weights, scale, bias, relu, residual,
                      cout == 1 ? nullptr : (unsigned short*)out, cout == 1 ? (float*)out : nullptr, cout, dilation, h,
                      w, ntx, nty);

@@ -8,6 +8,8 @@ libsfm_hip.so (include/sfm_hip.h):
   regularize  PSNet 3-D cost regularisation (dres0..classify) on the matrix cores; conv3_autograd with a float16
            backward (data and weight gradient) for training, batchnorm3_act_autograd (BatchNorm3d + ReLU + residual
            in float16, forward and backward)
+  context  PSNet's per-plane context stack and the full-resolution refinement stack on the matrix cores;
+           context_refine_autograd with a float16 backward (data and weight gradient of every stage)
   depth    correlation cost and the soft-argmin depth head; depth_head_autograd with a gradient into the cost
   synth    seeded synthetic KITTI-shaped inputs
   dist     one-process-per-GPU pair sharding and RCCL metric gather
@@ -16,7 +18,8 @@ libsfm_hip.so (include/sfm_hip.h):
 from . import _lib  # noqa: F401
 
 __all__ = ["ransac", "sweep", "regularize", "synth", "dist", "config", "validate", "plane_sweep_cost_autograd",
-           "inverse_warp_autograd", "depth_head_autograd", "conv3_autograd", "batchnorm3_act_autograd"]
+           "inverse_warp_autograd", "depth_head_autograd", "conv3_autograd", "batchnorm3_act_autograd",
+           "context_refine_autograd"]
 
 
 def __getattr__(name):
@@ -30,4 +33,7 @@ def __getattr__(name):
     if name in ("conv3_autograd", "batchnorm3_act_autograd"):
         from . import regularize
         return getattr(regularize, name)
+    if name == "context_refine_autograd":
+        from . import context
+        return context.context_refine_autograd
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -161,6 +161,17 @@ _SIGS = [
     ("sfm_context_pack_bf16", ctypes.c_int,
      [_c_dp, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
       _c_dp, _c_dp]),
+    ("sfm_conv2_wgrad_f16_workspace_bytes", ctypes.c_size_t,
+     [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    ("sfm_conv2_wgrad_f16", ctypes.c_int,
+     [_c_dp, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp,
+      ctypes.c_size_t, _c_dp]),
+    ("sfm_conv2_dgrad_f16", ctypes.c_int,
+     [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp,
+      _c_dp]),
+    ("sfm_context_unpack_grad_f16", ctypes.c_int,
+     [_c_dp, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+      _c_dp, _c_dp, _c_dp]),
     ("sfm_dep_context_pack_f16", ctypes.c_int,
      [_c_dp, _c_dp, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
       ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp]),

@@ -22,6 +22,10 @@ libsfm_hip.so or a GPU the call raises.
 
 as one ``sfm_dep_context_pack_*`` (the bilinear upsample fused in) and the same
 seven ``sfm_conv2_*`` launches per chunk of pairs.
+
+``context_refine_autograd`` is ``context_refine`` in float16 with a backward
+(csrc/context_bwd.hip): per stage ``sfm_conv2_wgrad_f16`` and
+``sfm_conv2_dgrad_f16``, then ``sfm_context_unpack_grad_f16``.
 """
 import weakref
 
@@ -333,3 +337,228 @@ def dep_context_refine(dep_convs, depth, feat, image, precision="fp16", max_scra
             if not whole:
                 out[b0:b0 + nb, 0].copy_(last)
     return out
+
+
+# --- the stack's backward in float16 (csrc/context_bwd.hip) -------------------------
+def pack_dgrad_weights2(weight):
+    """The weights that turn sfm_conv2_f16's kernel into the stage's data
+    gradient (sfm_conv2_dgrad_f16): Wd[t][ci][co] = W[co][ci][8 - t] as
+    [9, cin_pad, cout_pad], rows beyond cin and columns beyond cout zero.
+    Pure torch, any device and dtype."""
+    cout, cin = weight.shape[:2]
+    wd = weight.new_zeros(9, _pad32(cin), _pad32(cout))
+    wd[:, :cin, :cout] = weight.reshape(cout, cin, 9).flip(2).permute(2, 1, 0)
+    return wd
+
+
+def unpack_wgrad2(gwp, cout, cin):
+    """sfm_conv2_wgrad_f16's [9, cout_pad, cin_pad] result in the Conv2d
+    parameter's layout [cout, cin, 3, 3]; the padded rows and columns are
+    dropped.  Pure torch."""
+    return gwp[:, :cout, :cin].permute(1, 2, 0).reshape(cout, cin, 3, 3).contiguous()
+
+
+def _f16_cl(t, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float16 and t.is_contiguous() and
+            t.dim() == 4 and t.shape[-1] in _CHANNELS):
+        raise RuntimeError(f"{name} must be a contiguous [images, h, w, c] float16 device tensor, c in {_CHANNELS} "
+                           "(HIP path, no CPU fallback)")
+
+
+def conv2_wgrad_f16(x, grad_out, dilation):
+    """sfm_conv2_wgrad_f16: x [images, h, w, cin] and grad_out [images, h, w,
+    cout_pad], contiguous float16 device tensors -> [9, cout_pad, cin]
+    float32, reproducible bit for bit."""
+    _f16_cl(x, "x")
+    _f16_cl(grad_out, "grad_out")
+    n, h, w, cin = x.shape
+    if tuple(grad_out.shape[:3]) != (n, h, w):
+        raise RuntimeError("grad_out must have x's images, h and w")
+    cop = grad_out.shape[-1]
+    lib = _lib.load()
+    gw = torch.empty((9, cop, cin), dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(16, lib.sfm_conv2_wgrad_f16_workspace_bytes(n, cin, cop, h, w)), dtype=torch.uint8,
+                     device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.sfm_conv2_wgrad_f16(_lib.ptr(x), _lib.ptr(grad_out), n, cin, cop, h, w, int(dilation), _lib.ptr(gw),
+                                     _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device))
+        _lib.check(rc, "sfm_conv2_wgrad_f16")
+    return gw
+
+
+def conv2_dgrad_f16(grad_out, weights_d, dilation, act=None):
+    """sfm_conv2_dgrad_f16: grad_out [images, h, w, cout_pad] float16,
+    weights_d [9, cin_pad, cout_pad] float16 (``pack_dgrad_weights2``), act
+    [images, h, w, cin_pad] float16 or None -> [images, h, w, cin_pad]
+    float16, zero where act is not positive."""
+    _f16_cl(grad_out, "grad_out")
+    n, h, w, cop = grad_out.shape
+    if not (weights_d.is_cuda and weights_d.dtype == torch.float16 and weights_d.is_contiguous() and
+            weights_d.dim() == 3 and weights_d.shape[0] == 9 and weights_d.shape[2] == cop and
+            weights_d.shape[1] in _CHANNELS):
+        raise RuntimeError(f"weights_d must be a contiguous [9, cin_pad, {cop}] float16 device tensor")
+    cip = weights_d.shape[1]
+    if act is not None:
+        _f16_cl(act, "act")
+        if tuple(act.shape) != (n, h, w, cip):
+            raise RuntimeError(f"act must be [{n}, {h}, {w}, {cip}]")
+    out = torch.empty((n, h, w, cip), dtype=torch.float16, device=grad_out.device)
+    with torch.cuda.device(grad_out.device):
+        rc = _lib.load().sfm_conv2_dgrad_f16(_lib.ptr(grad_out), n, cop, h, w, _lib.ptr(weights_d), cip, int(dilation),
+                                             _lib.ptr(act), _lib.ptr(out), _lib.stream_ptr(grad_out.device))
+        _lib.check(rc, "sfm_conv2_dgrad_f16")
+    return out
+
+
+def context_unpack_grad(g0, grad_out, l0, first, grad_ctx, grad_planes):
+    """sfm_context_unpack_grad_f16: g0 [B, nl, h, w, 64] float16, the first
+    stage's data gradient for planes l0 .. l0+nl-1; grad_out and grad_planes
+    [B, L, h, w] float32; grad_ctx [B, 32, h, w] float32, written when
+    ``first`` and added to otherwise.  In place; returns nothing."""
+    if not (g0.is_cuda and g0.dtype == torch.float16 and g0.is_contiguous() and g0.dim() == 5 and g0.shape[-1] == 64):
+        raise RuntimeError("g0 must be a contiguous [B, nl, h, w, 64] float16 device tensor")
+    B, nl, h, w, _ = g0.shape
+    for t, n in ((grad_out, "grad_out"), (grad_planes, "grad_planes")):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 4 and
+                t.shape[0] == B and tuple(t.shape[2:]) == (h, w)):
+            raise RuntimeError(f"{n} must be a contiguous [B, L, h, w] float32 device tensor")
+    L = grad_out.shape[1]
+    if grad_planes.shape[1] != L:
+        raise RuntimeError("grad_planes must have grad_out's shape")
+    if not (grad_ctx.is_cuda and grad_ctx.dtype == torch.float32 and grad_ctx.is_contiguous() and
+            tuple(grad_ctx.shape) == (B, 32, h, w)):
+        raise RuntimeError("grad_ctx must be a contiguous [B, 32, h, w] float32 device tensor")
+    with torch.cuda.device(g0.device):
+        rc = _lib.load().sfm_context_unpack_grad_f16(_lib.ptr(g0), _lib.ptr(grad_out), B, L, int(l0), nl, h, w,
+                                                     1 if first else 0, _lib.ptr(grad_ctx), _lib.ptr(grad_planes),
+                                                     _lib.stream_ptr(g0.device))
+        _lib.check(rc, "sfm_context_unpack_grad_f16")
+
+
+class _ContextStack(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, convs, nl_max, ctx, costs, *weights):
+        B, _, L, h, w = costs.shape
+        dev = costs.device
+        packed = pack_context_stack(convs, dev, "fp16")
+        lib = _lib.load()
+        ctx32 = ctx.detach().float().contiguous()
+        planes = costs.detach().reshape(B, L, h, w).contiguous()
+        relu_out = torch.empty((B, L, h, w), dtype=torch.float32, device=dev)
+        saved = []                              # per chunk: the seven stages' float16 inputs
+        with torch.cuda.device(dev):
+            stream = _lib.stream_ptr(dev)
+            for l0 in range(0, L, nl_max):
+                nl = min(nl_max, L - l0)
+                x = torch.empty((B * nl, h, w, 64), dtype=torch.float16, device=dev)
+                _lib.check(lib.sfm_context_pack_f16(_lib.ptr(ctx32), _lib.ptr(planes), B, L, l0, nl, 32, h, w,
+                                                    _lib.ptr(x), stream), "sfm_context_pack")
+                acts = []
+                for lay in packed:
+                    acts.append(x)
+                    final = lay["cout"] == 1
+                    # the last stage without its residual, so that its ReLU output is kept; the fp32 "+ plane"
+                    # below gives the bits of the fused form
+                    y = torch.empty((B, nl, h, w), dtype=torch.float32, device=dev) if final else \
+                        torch.empty((B * nl, h, w, lay["cout"]), dtype=torch.float16, device=dev)
+                    rc = lib.sfm_conv2_f16(_lib.ptr(x), B * nl, lay["cin_pad"], h, w, _lib.ptr(lay["w"]), lay["cout"],
+                                           lay["dilation"], _lib.ptr(lay["scale"]), _lib.ptr(lay["bias"]),
+                                           1 if lay["relu"] else 0, None, _lib.ptr(y), stream)
+                    _lib.check(rc, "sfm_conv2")
+                    x = y
+                relu_out[:, l0:l0 + nl].copy_(x)
+                saved.append(acts)
+        fctx.saved, fctx.relu_out, fctx.nl_max = saved, relu_out, nl_max
+        fctx.meta = [(lay["cin"], lay["cout"], lay["dilation"], lay["relu"]) for lay in packed]
+        fctx.ctx_dtype = ctx.dtype
+        fctx.save_for_backward(*weights)
+        return (relu_out + planes).view(B, 1, L, h, w)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, grad):
+        weights = fctx.saved_tensors
+        B, _, L, h, w = grad.shape
+        dev = grad.device
+        go = grad.detach().float().reshape(B, L, h, w).contiguous()
+        nl_max, meta = fctx.nl_max, fctx.meta
+        wds = [pack_dgrad_weights2(wt.detach().float()).half().contiguous() for wt in weights]
+        gws = [None] * len(weights)
+        grad_ctx = torch.empty((B, 32, h, w), dtype=torch.float32, device=dev)
+        grad_planes = torch.empty((B, L, h, w), dtype=torch.float32, device=dev)
+        for k, l0 in enumerate(range(0, L, nl_max)):        # ascending: the unpack kernel's summation order
+            nl = min(nl_max, L - l0)
+            acts = fctx.saved[k]
+            # the last stage: through its ReLU, as channel 0 of a zero-padded 32-channel tensor
+            gl = go[:, l0:l0 + nl]
+            if meta[-1][3]:
+                gl = torch.where(fctx.relu_out[:, l0:l0 + nl] > 0, gl, torch.zeros_like(gl))
+            g = torch.zeros((B * nl, h, w, 32), dtype=torch.float16, device=dev)
+            g[..., 0] = gl.reshape(B * nl, h, w)
+            for s in range(len(meta) - 1, -1, -1):
+                dil = meta[s][2]
+                gw = conv2_wgrad_f16(acts[s], g, dil)
+                gws[s] = gw if gws[s] is None else gws[s] + gw
+                g = conv2_dgrad_f16(g, wds[s], dil, acts[s] if s > 0 else None)
+            context_unpack_grad(g.view(B, nl, h, w, 64), go, l0, k == 0, grad_ctx, grad_planes)
+            fctx.saved[k] = None                            # a chunk's activations are done with
+        out_w = [unpack_wgrad2(gw, m[1], m[0]).to(wt.dtype) for gw, m, wt in zip(gws, meta, weights)]
+        return (None, None, grad_ctx.to(fctx.ctx_dtype), grad_planes.view(B, 1, L, h, w)) + tuple(out_w)
+
+
+def context_refine_autograd(convs, ctx, costs, max_scratch_bytes=1 << 30):
+    """``context_refine`` (float16) with a backward on libsfm_hip: one
+    autograd function over the whole stack, ctx [B, 32, h, w] (any float
+    dtype), costs [B, 1, L, h, w] fp32 -> [B, 1, L, h, w] fp32, the bits of
+    ``context_refine(convs, ctx, costs, "fp16")``.  Gradients flow to the seven
+    Conv2d weights (float32, the parameters' layout), ``ctx`` and ``costs``.
+
+    Forward: the same ``sfm_context_pack_f16`` and seven ``sfm_conv2_f16``
+    launches per chunk of ``planes_per_chunk`` planes; every stage's float16
+    input is kept, and the last stage runs without its residual so that its
+    ReLU output is kept too (the fp32 "+ plane" is a torch add).  Backward,
+    per chunk in ascending plane order and from the last stage to the first:
+    ``sfm_conv2_wgrad_f16``, ``sfm_conv2_dgrad_f16`` masked by the saved
+    activation, then ``sfm_context_unpack_grad_f16``; weight gradients are
+    added over the chunks in fp32.  The ``ctx`` and ``costs`` gradients have
+    the same bits for any chunking.
+
+    Memory: the saved activations are 64 + 128 + 128 + 128 + 96 + 64 + 32 =
+    640 float16 channels, 1280 bytes per pixel and plane, for all L planes
+    until the backward has run: 4.8 GB per KITTI pair at L = 128 (94 x 311);
+    ``max_scratch_bytes`` bounds only the chunk's transient buffers.
+
+    Refused with a named reason: CPU tensors, a call outside float16 CUDA
+    autocast, a non-stock layout, and any BatchNorm2d stage (in training mode
+    its batch statistics have no backward here; in eval mode the folded affine
+    has none either)."""
+    for t, n in ((ctx, "ctx"), (costs, "costs")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise RuntimeError(f"context_refine_autograd needs device tensors (HIP path, no CPU fallback): {n}")
+    if not torch.is_autocast_enabled() or _autocast_gpu_dtype() != torch.float16:
+        raise RuntimeError("context_refine_autograd computes the stack in float16: call it under "
+                           "torch.autocast('cuda', torch.float16)")
+    if costs.dim() != 5 or costs.shape[1] != 1 or costs.dtype != torch.float32:
+        raise RuntimeError("costs must be [B, 1, L, h, w] float32")
+    B, _, L, h, w = costs.shape
+    if ctx.dim() != 4 or tuple(ctx.shape) != (B, 32, h, w) or not ctx.is_floating_point():
+        raise RuntimeError(f"ctx must be [{B}, 32, {h}, {w}] floating point")
+    if not stock_layout(convs):
+        _stages(convs)          # raises the named reason, if that is it
+        raise ContextStackError("the context stack must take 33 channels and end in one")
+    stages = _stages(convs)
+    for i, (conv, bn, relu) in enumerate(stages):
+        if bn is not None:
+            mode = "in training mode (batch statistics)" if bn.training else "in eval mode (a folded affine)"
+            raise ContextStackError(f"stage {i}: BatchNorm2d {mode} has no backward on the float16 route")
+        if conv.weight.dtype != torch.float32 or conv.weight.device != costs.device:
+            raise ContextStackError(f"stage {i}: the weight must be float32 on the tensors' device")
+    nl_max = planes_per_chunk(B, h, w, L, max_scratch_bytes)
+    return _ContextStack.apply(convs, nl_max, ctx, costs, *[conv.weight for conv, _, _ in stages])
+
+
+def _autocast_gpu_dtype():
+    """torch.get_autocast_gpu_dtype(), by its newer name where torch has it."""
+    if hasattr(torch, "get_autocast_dtype"):
+        return torch.get_autocast_dtype("cuda")
+    return torch.get_autocast_gpu_dtype()

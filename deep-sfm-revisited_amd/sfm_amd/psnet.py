@@ -23,6 +23,9 @@ and runs its forward with the hot path on libsfm_hip:
                       dres0..4 / classify under float16 autocast       sfm_conv3_f16 / sfm_conv3_wgrad_f16 (HIP MFMA)
                       with ``regularize_grad`` "fp16"                   between torch's BatchNorm3d, or with
                       ``regularize_norm`` "hip"                        sfm_bn3_stats / _apply / _backward_f16 (HIP)
+                      convs under float16 autocast with                sfm_conv2_f16 / sfm_conv2_dgrad_f16 /
+                      ``context_grad`` "fp16"                          sfm_conv2_wgrad_f16 (HIP MFMA),
+                                                                       sfm_context_pack_f16 / _unpack_grad_f16 (HIP)
   dep_convs           full-resolution depth refinement (PSNET_DEP_CONTEXT, 218-225): bilinear upsample + cat
                       sfm_dep_context_pack_* (HIP), the stack      sfm_conv2_* (HIP MFMA) under float16 autocast
                       in eval mode (``dep_context_precision``); else   torch (MIOpen)
@@ -39,7 +42,7 @@ import torch.nn.functional as F
 
 from . import feature as _feature
 from .config import cfg as _default_cfg
-from .context import context_refine, dep_context_refine, dep_stock_layout, stock_layout
+from .context import context_refine, context_refine_autograd, dep_context_refine, dep_stock_layout, stock_layout
 from .depth import depth_head, depth_head_autograd
 from .regularize import CostRegularization, f16_features, fused_channels_last, sweep_regularize_fused
 from .sweep import plane_sweep_cost, plane_sweep_cost_autograd, quarter_intrinsics
@@ -215,14 +218,21 @@ class PSNet(CostRegularization):
     runs the stack's BatchNorm3d, ReLU and residual adds: "torch" (default: the
     modules and torch ops) or "hip" (opt-in: ``batchnorm3_act_autograd``,
     sfm_bn3_* in both directions; profiles/stack_norm_ab.txt); it has no effect
-    on the "torch" route.
+    on the "torch" route.  ``context_grad`` selects how the differentiable
+    route runs the context stack ``convs``: "torch" (default: the modules) or
+    "fp16" (opt-in: ``sfm_amd.context.context_refine_autograd``, every stage
+    forward and backward on libsfm_hip in float16, at the cost of 1280 bytes
+    of saved activations per pixel and plane; needs float16 CUDA autocast at
+    the call and raises without it; a stack with BatchNorm2d, cfg.CONTEXT_BN,
+    is refused; profiles/context_bwd_ab.txt).  ``dep_convs`` stays with the
+    modules.
     Everything else is unchanged bit for bit: calls under ``torch.no_grad()``
     in either mode, and the float16 eval routes, whose HIP features carry no
     grad and so never enter the differentiable route."""
 
     def __init__(self, nlabel, mindepth=None, cfg=None, feature_fn=None, cost_dtype=torch.float32,
                  conv_precision="auto", context_precision="auto", dep_context_precision="auto",
-                 feature_precision="auto", regularize_grad="auto", regularize_norm="torch"):
+                 feature_precision="auto", regularize_grad="auto", regularize_norm="torch", context_grad="torch"):
         super().__init__(64)
         c = _default_cfg if cfg is None else cfg
         if c.get("COST_BY_COLOR", False) or c.get("COST_BY_COLOR_WITH_FEAT", False):
@@ -251,6 +261,9 @@ class PSNet(CostRegularization):
         if regularize_norm not in ("torch", "hip"):
             raise ValueError(f"unknown regularize_norm {regularize_norm!r}")
         self.regularize_norm = regularize_norm
+        if context_grad not in ("torch", "fp16"):
+            raise ValueError(f"unknown context_grad {context_grad!r}")
+        self.context_grad = context_grad
         self.feature_extraction = FeatureExtraction() if feature_fn is None else feature_fn
         if c.get("IND_CONTEXT", False):
             self.context_net = FeatureExtraction()
@@ -367,6 +380,19 @@ class PSNet(CostRegularization):
             return p
         return "fp16" if half and STACK_BWD_HIP and self._stock_regularizer() else "torch"
 
+    def context_grad_route(self, device=None):
+        """How the differentiable route runs the context stack at this call:
+        "torch" or "fp16" (see ``context_grad``)."""
+        p = self.context_grad
+        if p == "torch":
+            return p
+        on_gpu = device is not None and torch.device(device).type == "cuda"
+        if not (on_gpu and torch.is_autocast_enabled() and _autocast_gpu_dtype() == torch.float16):
+            raise RuntimeError("context_grad='fp16' computes the context stack in float16 on the GPU: call the model "
+                               "on a CUDA device under torch.autocast('cuda', torch.float16), or leave "
+                               "context_grad at 'torch'")
+        return p
+
     def _regularize_modules(self, cost):
         """dres0..4 and classify as PSNet.py:160-165 calls them: the modules themselves, which carry a gradient
         and whose BatchNorm follows self.training (the matrix-core stack folds it and has no backward)."""
@@ -437,7 +463,14 @@ class PSNet(CostRegularization):
         if c.get("PSNET_CONTEXT", True):
             route = self._grad_stack_route("context_precision", self.context_route, costs.device) if diff else \
                 self.context_route(costs.device)
-        if route in ("fp16", "bf16"):
+            if diff and self.context_grad_route(costs.device) == "fp16":
+                route = "grad-fp16"
+        if route == "grad-fp16":
+            # the stack with a backward on libsfm_hip: the planes b-major, as on the forward-only HIP route
+            ctx = self._features("context_net", [ref])[0] if c.get("IND_CONTEXT", False) else ref_raw  # 177-178
+            dep_src = ctx
+            costss = context_refine_autograd(self.convs, ctx, costs.float())
+        elif route in ("fp16", "bf16"):
             # the stack on libsfm_hip: the features in whatever dtype they arrive (no float32 copy), the planes
             # b-major, so the result is already the [B, L, h, w] volume the head reads
             ctx = self._features("context_net", [ref])[0] if c.get("IND_CONTEXT", False) else ref_raw  # 177-178

@@ -784,6 +784,78 @@ int sfm_context_pack_f16(const float* ctx, const float* planes, int batch, int n
 int sfm_context_pack_bf16(const float* ctx, const float* planes, int batch, int nlabel, int l0, int nl, int channels,
                           int h, int w, void* out, void* stream);
 
+/* Training the context stack in float16 (the reference trains under float16
+ * autocast, cfgs/kitti.yml:10 MIXED_PREC): the weight gradient of one raw
+ * stage of the stack (convtext, models/PSNet.py:17-26; the seven stages 64-71;
+ * applied per plane at 175-190), on v_mfma_f32_32x32x16_f16 with fp32
+ * accumulation:
+ *   grad_weights[tap][co][ci] = sum over image, y, x of
+ *       grad_out[img, y, x, co] in[img, y + (kh-1) dil, x + (kw-1) dil, ci]
+ * (zero outside the image; tap = kh*3 + kw).
+ *   in           [dev] images x h x w x cin float16, cin 32, 64, 96 or 128: the
+ *                stage's input, as sfm_conv2_f16 read it;
+ *   grad_out     [dev] images x h x w x cout_pad float16, cout_pad 32, 64, 96 or
+ *                128: the gradient of the raw convolution's output.  The cout 1
+ *                stage passes its gradient as channel 0 of a zero-padded
+ *                32-channel tensor and reads row co = 0;
+ *   dilation     1..16;
+ *   grad_weights [dev] 9 x cout_pad x cin float32, sfm_conv2_f16's pack layout;
+ *   workspace    [dev] sfm_conv2_wgrad_f16_workspace_bytes(images, cin, cout_pad,
+ *                h, w) bytes, 16-byte aligned: one 9 x cout_pad x cin float32
+ *                partial sum per accumulating block.
+ * Every pointer 16-byte aligned; grad_weights and workspace overlap neither
+ * each other nor an input.  A fixed grid of accumulating blocks walks
+ * contiguous ranges of tiles (4 rows x 64 columns of one image), each block
+ * writing one partial, and a second launch adds the partials in block order: no
+ * float atomics, so two calls give the same bits.  The number of blocks is
+ * min(tiles, 512), or the tuning key conv2_wgrad_blocks (1..4096; 0, default:
+ * as above) -- launch shape only, read by both functions, and like
+ * conv_wgrad_blocks taken by sfm_tune_set / sfm_tune_get without being
+ * enumerated by sfm_tune_key.  Profile name "conv2_wgrad". */
+size_t sfm_conv2_wgrad_f16_workspace_bytes(int images, int cin, int cout_pad, int h, int w);
+int sfm_conv2_wgrad_f16(const void* in, const void* grad_out, int images, int cin, int cout_pad, int h, int w,
+                        int dilation, float* grad_weights, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The data gradient of the same stage (models/PSNet.py:17-26, 64-71, 175-190)
+ * through the previous stage's ReLU.  With W[co][ci][tap] the stage's weights,
+ *   grad_in[p, ci] = sum over tap, co of W[co][ci][tap] grad_out[p - (tap - 1) dil, co]
+ * is sfm_conv2_f16's kernel on grad_out with the flipped, transposed weights
+ * Wd[t][ci][co] = W[co][ci][8 - t] at the same dilation, and the epilogue
+ *   grad_in[p, c] = act[p, c] > 0 ? f16(acc) : 0
+ * a select, not a product: a non-finite gradient under a zero activation gives
+ * +0, one under a positive activation comes through (a GradScaler sees it).
+ *   grad_out [dev] images x h x w x cout_pad float16, cout_pad 32, 64, 96 or 128
+ *            (the cout 1 stage: zero-padded to 32 channels, as above);
+ *   weights  [dev] 9 x cin_pad x cout_pad float16: Wd, rows beyond cin and
+ *            columns beyond cout zero;
+ *   act      [dev] images x h x w x cin_pad float16: the stage's saved input,
+ *            which is the previous stage's ReLU output; NULL (the first stage):
+ *            nothing is masked;
+ *   grad_in  [dev] images x h x w x cin_pad float16, cin_pad 32, 64, 96 or 128.
+ * Every pointer 16-byte aligned; grad_in aliases no input.  Profile name
+ * "conv2_dgrad". */
+int sfm_conv2_dgrad_f16(const void* grad_out, int images, int cout_pad, int h, int w, const void* weights, int cin_pad,
+                        int dilation, const void* act, void* grad_in, void* stream);
+
+/* The first stage's data gradient back to PSNet's tensors: the backward of
+ * sfm_context_pack_f16 and of the "+ plane" of models/PSNet.py:190 (the stack
+ * of 17-26, 64-71, applied at 175-190), for planes l0 .. l0+nl-1 of every pair.
+ *   grad_in0    [dev] batch x nl x h x w x 64 float16, 16-byte aligned: channels
+ *               0..31 the feature gradient per plane, channel 32 the plane's,
+ *               33..63 ignored;
+ *   grad_out    [dev] batch x nlabel x h x w float32: the gradient of the stack's
+ *               output;
+ *   grad_ctx    [dev] batch x 32 x h x w float32: the planes' feature gradients
+ *               added in ascending plane order in float32, onto the value
+ *               already there, or onto zero with first != 0;
+ *   grad_planes [dev] batch x nlabel x h x w float32:
+ *               [b][l0 + l] = f32(grad_in0[b][l][.., 32]) + grad_out[b][l0 + l].
+ * Called chunk after chunk in ascending plane order (first != 0 for the first)
+ * the result has the same bits for any chunking.  Profile name
+ * "context_unpack_grad". */
+int sfm_context_unpack_grad_f16(const void* grad_in0, const float* grad_out, int batch, int nlabel, int l0, int nl,
+                                int h, int w, int first, float* grad_ctx, float* grad_planes, void* stream);
+
 /* The first-stage input of the full-resolution depth refinement stack
  * dep_convs (models/PSNet.py:218-221: up_feat = interpolate(refimg_fea,
  * [H, W], bilinear, align_corners=True); cat((depth, up_feat, ref))) for

@@ -33,7 +33,9 @@
 //
 // The data gradient is k_conv2 itself (conv2_tile.h) on flipped weights with
 // the MASK epilogue; k_context_unpack_grad carries the first stage's gradient
-// back to PSNet's tensors.
+// back to PSNet's tensors.  The full-resolution refinement stack dep_convs
+// (PSNet.py:218-221) runs the same two products; k_dep_unpack_grad is the
+// backward of its pack's bilinear upsample into the features.
 #include <string>
 #include "conv2_tile.h"
 
@@ -221,6 +223,80 @@ __global__ __launch_bounds__(256) void k_context_unpack_grad(const unsigned shor
   for (int j = 0; j < 8; ++j) c[(int64_t)j * hw] = s[j];
 }
 
+// The first destination index d in [0, n_dst) whose forward source index
+// min((int)(scale d), n_src - 1) -- k_dep_pack's expression (context.hip) -- is
+// at least t, or n_dst: a bisection over the forward's own expression, which
+// is monotone in d (a rounded product by a non-negative constant, a
+// truncation, a min).
+__device__ __forceinline__ int dep_first_at_least(double scale, int n_src, int n_dst, int t) {
+  int lo = 0, hi = n_dst;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (min((int)(scale * (double)mid), n_src - 1) >= t) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+// The backward of k_dep_pack's bilinear upsample (models/PSNet.py:218-221) into
+// the features: g [nb][H][W][64] is the first stage's data gradient, channels
+// 1..32 the upsampled features'.  A gather: one thread per (pair, source pixel
+// (i, j), 16-byte chunk 0..4 of g).  The destination rows that read source row
+// i are those whose y0 is i - 1 or i (y1 = y0 + (y0 < h - 1)), a contiguous
+// range found by bisection on the forward's index expression; every row and
+// column of the range is then weighted with the forward's own y0, y1, ly0, ly1
+// in float64,
+//   wy = ly0 [y0 == i] + ly1 [y1 == i],
+// so no inverted formula can disagree with k_dep_pack at a rounding boundary.
+// Rows ascending, then columns ascending, summed in float64 and rounded once to
+// float32: no atomics, the same bits from call to call and for any chunking.
+// Slot s of chunk k is feature 8 k + s - 1 (k_dep_pack's layout): chunk 0 writes
+// features 0..6, chunks 1..3 eight each, chunk 4 feature 31.  A source pixel
+// that no destination reads is written as +0.
+__global__ __launch_bounds__(256) void k_dep_unpack_grad(const unsigned short* __restrict__ g, int b0, int h, int w,
+                                                         int H, int W, double sy, double sx, int64_t total,
+                                                         float* __restrict__ grad_feat) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  const int chunk = (int)(t % 5);
+  const int64_t sp = t / 5;                       // img * h * w + i * w + j
+  const int hw = h * w;
+  const int p = (int)(sp % hw), img = (int)(sp / hw);
+  const int i = p / w, j = p - i * w;
+  const int ya = dep_first_at_least(sy, h, H, i - 1), yb = dep_first_at_least(sy, h, H, i + 1);
+  const int xa = dep_first_at_least(sx, w, W, j - 1), xb = dep_first_at_least(sx, w, W, j + 1);
+  const unsigned short* gp = g + (int64_t)img * H * W * 64 + chunk * 8;
+  double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int y = ya; y < yb; ++y) {
+    const double fy = sy * (double)y;
+    const int y0 = min((int)fy, h - 1);
+    const int y1 = y0 + (y0 < h - 1);
+    const double ly1 = fy - (double)y0, ly0 = 1.0 - ly1;
+    const double wy = (y0 == i ? ly0 : 0.0) + (y1 == i ? ly1 : 0.0);
+    const unsigned short* row = gp + (int64_t)y * W * 64;
+    for (int x = xa; x < xb; ++x) {
+      const double fx = sx * (double)x;
+      const int x0 = min((int)fx, w - 1);
+      const int x1 = x0 + (x0 < w - 1);
+      const double lx1 = fx - (double)x0, lx0 = 1.0 - lx1;
+      const double wx = (x0 == j ? lx0 : 0.0) + (x1 == j ? lx1 : 0.0);
+      const double wt = wy * wx;
+      const uint4 v = *reinterpret_cast<const uint4*>(row + (int64_t)x * 64);
+      const unsigned u[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        s[2 * k] = s[2 * k] + wt * (double)ActCvt<true>::to_f((unsigned short)(u[k] & 0xffffu));
+        s[2 * k + 1] = s[2 * k + 1] + wt * (double)ActCvt<true>::to_f((unsigned short)(u[k] >> 16));
+      }
+    }
+  }
+  float* out = grad_feat + (int64_t)(b0 + img) * 32 * hw + p;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int c = chunk * 8 + k - 1;              // slot k of this chunk is feature c
+    if (c >= 0 && c < 32) out[(int64_t)c * hw] = (float)s[k];
+  }
+}
+
 struct Wgrad2Plan {
   int ntx, nty, blocks, ng;
   int64_t ntiles;
@@ -369,6 +445,30 @@ int sfm_context_unpack_grad_f16(const void* grad_in0, const float* grad_out, int
   ProfScope ps("context_unpack_grad", s);
   hipLaunchKernelGGL(k_context_unpack_grad, dim3((unsigned)nblk), dim3(256), 0, s, (const unsigned short*)grad_in0,
                      grad_out, nlabel, l0, nl, h * w, total, first ? 1 : 0, grad_ctx, grad_planes);
+  SFM_LAUNCHED();
+  return SFM_OK;
+}
+
+int sfm_dep_context_unpack_grad_f16(const void* grad_in0, int batch, int b0, int nb, int channels, int h, int w, int H,
+                                    int W, float* grad_feat, void* stream) {
+  SFM_REQUIRE(grad_in0 && grad_feat, "null pointer argument");
+  SFM_REQUIRE(channels == 32, "the refinement stack's first layer takes 1 depth + 32 feature + 3 image channels");
+  SFM_REQUIRE(batch >= 1 && h >= 1 && w >= 1 && H >= 1 && W >= 1, "invalid refinement shape");
+  SFM_REQUIRE(b0 >= 0 && nb >= 1 && b0 <= batch - nb, "pair range outside the batch");
+  SFM_REQUIRE((int64_t)h * w < ((int64_t)1 << 28), "feature map too large");
+  SFM_REQUIRE((int64_t)H * W < ((int64_t)1 << 28), "image too large");
+  SFM_REQUIRE(((uintptr_t)grad_in0 & 15) == 0, "the stage gradient must be 16-byte aligned");
+  SFM_REQUIRE(((uintptr_t)grad_feat & 3) == 0, "float operands must be 4-byte aligned");
+  const int64_t total = (int64_t)nb * h * w * 5;
+  const int64_t nblk = (total + 255) / 256;
+  SFM_REQUIRE(nblk < ((int64_t)1 << 31), "refinement unpack grid too large");
+  // k_dep_pack's scales: torch's area_pixel_compute_scale for align_corners=True, in float64
+  const double sy = H > 1 ? (double)(h - 1) / (double)(H - 1) : 0.0;
+  const double sx = W > 1 ? (double)(w - 1) / (double)(W - 1) : 0.0;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps("dep_context_unpack_grad", s);
+  hipLaunchKernelGGL(k_dep_unpack_grad, dim3((unsigned)nblk), dim3(256), 0, s, (const unsigned short*)grad_in0, b0, h, w,
+                     H, W, sy, sx, total, grad_feat);
   SFM_LAUNCHED();
   return SFM_OK;
 }

@@ -9,7 +9,8 @@ libsfm_hip.so (include/sfm_hip.h):
            backward (data and weight gradient) for training, batchnorm3_act_autograd (BatchNorm3d + ReLU + residual
            in float16, forward and backward)
   context  PSNet's per-plane context stack and the full-resolution refinement stack on the matrix cores;
-           context_refine_autograd with a float16 backward (data and weight gradient of every stage)
+           context_refine_autograd and dep_context_refine_autograd with a float16 backward (data and weight
+           gradient of every stage; dep_context_unpack_grad, the bilinear upsample's backward)
   depth    correlation cost and the soft-argmin depth head; depth_head_autograd with a gradient into the cost
   synth    seeded synthetic KITTI-shaped inputs
   dist     one-process-per-GPU pair sharding and RCCL metric gather
@@ -19,7 +20,7 @@ from . import _lib  # noqa: F401
 
 __all__ = ["ransac", "sweep", "regularize", "synth", "dist", "config", "validate", "plane_sweep_cost_autograd",
            "inverse_warp_autograd", "depth_head_autograd", "conv3_autograd", "batchnorm3_act_autograd",
-           "context_refine_autograd"]
+           "context_refine_autograd", "dep_context_refine_autograd", "dep_context_unpack_grad"]
 
 
 def __getattr__(name):
@@ -33,7 +34,7 @@ def __getattr__(name):
     if name in ("conv3_autograd", "batchnorm3_act_autograd"):
         from . import regularize
         return getattr(regularize, name)
-    if name == "context_refine_autograd":
+    if name in ("context_refine_autograd", "dep_context_refine_autograd", "dep_context_unpack_grad"):
         from . import context
-        return context.context_refine_autograd
+        return getattr(context, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -178,6 +178,9 @@ _SIGS = [
     ("sfm_dep_context_pack_bf16", ctypes.c_int,
      [_c_dp, _c_dp, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
       ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp]),
+    ("sfm_dep_context_unpack_grad_f16", ctypes.c_int,
+     [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+      ctypes.c_int, _c_dp, _c_dp]),
     ("sfm_conv2x_f16", ctypes.c_int,
      [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
       ctypes.c_int, _c_dp, _c_dp, ctypes.c_int, _c_dp, _c_dp, _c_dp]),

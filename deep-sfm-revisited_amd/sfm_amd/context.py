@@ -26,6 +26,9 @@ seven ``sfm_conv2_*`` launches per chunk of pairs.
 ``context_refine_autograd`` is ``context_refine`` in float16 with a backward
 (csrc/context_bwd.hip): per stage ``sfm_conv2_wgrad_f16`` and
 ``sfm_conv2_dgrad_f16``, then ``sfm_context_unpack_grad_f16``.
+``dep_context_refine_autograd`` is the same for ``dep_context_refine``; its
+last step is ``sfm_dep_context_unpack_grad_f16``, the backward of the bilinear
+upsample into the features.
 """
 import weakref
 
@@ -555,6 +558,170 @@ def context_refine_autograd(convs, ctx, costs, max_scratch_bytes=1 << 30):
             raise ContextStackError(f"stage {i}: the weight must be float32 on the tensors' device")
     nl_max = planes_per_chunk(B, h, w, L, max_scratch_bytes)
     return _ContextStack.apply(convs, nl_max, ctx, costs, *[conv.weight for conv, _, _ in stages])
+
+
+# --- dep_convs' backward in float16 (csrc/context_bwd.hip) --------------------------
+def dep_context_unpack_grad(g0, b0, grad_feat):
+    """sfm_dep_context_unpack_grad_f16: g0 [nb, H, W, 64] float16, the first
+    stage's data gradient for pairs b0 .. b0+nb-1 (channels 1..32 the upsampled
+    features'); grad_feat [B, 32, h, w] float32, whose pairs b0 .. b0+nb-1 are
+    written with the backward of the bilinear align_corners=True upsample, the
+    others left as they are.  In place; returns nothing."""
+    if not (isinstance(g0, torch.Tensor) and g0.is_cuda and g0.dtype == torch.float16 and g0.is_contiguous() and
+            g0.dim() == 4 and g0.shape[-1] == 64):
+        raise RuntimeError("g0 must be a contiguous [nb, H, W, 64] float16 device tensor (HIP path, no CPU fallback)")
+    nb, H, W, _ = g0.shape
+    if not (isinstance(grad_feat, torch.Tensor) and grad_feat.is_cuda and grad_feat.dtype == torch.float32 and
+            grad_feat.is_contiguous() and grad_feat.dim() == 4 and grad_feat.shape[1] == 32 and
+            grad_feat.device == g0.device):
+        raise RuntimeError("grad_feat must be a contiguous [B, 32, h, w] float32 tensor on g0's device")
+    B, _, h, w = grad_feat.shape
+    with torch.cuda.device(g0.device):
+        rc = _lib.load().sfm_dep_context_unpack_grad_f16(_lib.ptr(g0), B, int(b0), nb, 32, h, w, H, W,
+                                                         _lib.ptr(grad_feat), _lib.stream_ptr(g0.device))
+        _lib.check(rc, "sfm_dep_context_unpack_grad_f16")
+
+
+class _DepContextStack(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, dep_convs, nb_max, depth, feat, image, *weights):
+        B, _, H, W = depth.shape
+        h, w = feat.shape[2:]
+        dev = depth.device
+        packed = pack_context_stack(dep_convs, dev, "fp16")
+        lib = _lib.load()
+        depth32 = depth.detach().contiguous()
+        feat_c = feat.detach().contiguous()
+        image32 = image.detach().float().contiguous()
+        relu_out = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+        saved = []                              # per chunk: the seven stages' float16 inputs
+        with torch.cuda.device(dev):
+            stream = _lib.stream_ptr(dev)
+            for b0 in range(0, B, nb_max):
+                nb = min(nb_max, B - b0)
+                x = torch.empty((nb, H, W, 64), dtype=torch.float16, device=dev)
+                _lib.check(lib.sfm_dep_context_pack_f16(_lib.ptr(depth32), _lib.ptr(feat_c), _FEAT_DTYPE[feat_c.dtype],
+                                                        _lib.ptr(image32), B, b0, nb, 32, h, w, H, W, _lib.ptr(x),
+                                                        stream), "sfm_dep_context_pack")
+                acts = []
+                for lay in packed:
+                    acts.append(x)
+                    final = lay["cout"] == 1
+                    # the last stage without its residual, so that its ReLU output is kept; the fp32 "+ depth"
+                    # below gives the bits of the fused form.  A chunk writes a buffer of its own, 16-byte aligned.
+                    if final:
+                        y = relu_out if nb == B else torch.empty((nb, 1, H, W), dtype=torch.float32, device=dev)
+                    else:
+                        y = torch.empty((nb, H, W, lay["cout"]), dtype=torch.float16, device=dev)
+                    rc = lib.sfm_conv2_f16(_lib.ptr(x), nb, lay["cin_pad"], H, W, _lib.ptr(lay["w"]), lay["cout"],
+                                           lay["dilation"], _lib.ptr(lay["scale"]), _lib.ptr(lay["bias"]),
+                                           1 if lay["relu"] else 0, None, _lib.ptr(y), stream)
+                    _lib.check(rc, "sfm_conv2")
+                    x = y
+                if nb != B:
+                    relu_out[b0:b0 + nb].copy_(x)
+                saved.append(acts)
+        fctx.saved, fctx.relu_out, fctx.nb_max = saved, relu_out, nb_max
+        fctx.meta = [(lay["cin"], lay["cout"], lay["dilation"], lay["relu"]) for lay in packed]
+        fctx.feat_shape, fctx.feat_dtype = tuple(feat.shape), feat.dtype
+        fctx.save_for_backward(*weights)
+        return relu_out + depth32
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, grad):
+        weights = fctx.saved_tensors
+        B, _, H, W = grad.shape
+        dev = grad.device
+        go = grad.detach().float().contiguous()
+        nb_max, meta = fctx.nb_max, fctx.meta
+        wds = [pack_dgrad_weights2(wt.detach().float()).half().contiguous() for wt in weights]
+        gws = [None] * len(weights)
+        grad_feat = torch.empty(fctx.feat_shape, dtype=torch.float32, device=dev)
+        for k, b0 in enumerate(range(0, B, nb_max)):        # ascending pair order
+            nb = min(nb_max, B - b0)
+            acts = fctx.saved[k]
+            # the last stage: through its ReLU, as channel 0 of a zero-padded 32-channel tensor
+            gl = go[b0:b0 + nb, 0]
+            if meta[-1][3]:
+                gl = torch.where(fctx.relu_out[b0:b0 + nb, 0] > 0, gl, torch.zeros_like(gl))
+            g = torch.zeros((nb, H, W, 32), dtype=torch.float16, device=dev)
+            g[..., 0] = gl
+            for s in range(len(meta) - 1, -1, -1):
+                dil = meta[s][2]
+                gw = conv2_wgrad_f16(acts[s], g, dil)
+                gws[s] = gw if gws[s] is None else gws[s] + gw
+                g = conv2_dgrad_f16(g, wds[s], dil, acts[s] if s > 0 else None)
+            dep_context_unpack_grad(g, b0, grad_feat)
+            fctx.saved[k] = None                            # a chunk's activations are done with
+        out_w = [unpack_wgrad2(gw, m[1], m[0]).to(wt.dtype) for gw, m, wt in zip(gws, meta, weights)]
+        # depth: the "+ depth" residual alone (the cat reads depth.detach()); image: none
+        return (None, None, grad, grad_feat.to(fctx.feat_dtype), None) + tuple(out_w)
+
+
+def dep_context_refine_autograd(dep_convs, depth, feat, image, max_scratch_bytes=1 << 30):
+    """``dep_context_refine`` (float16) with a backward on libsfm_hip: one
+    autograd function over the whole full-resolution stack
+    (PSNet.py:218-221), depth [B, 1, H, W] fp32, feat [B, 32, h, w] float16,
+    bfloat16 or float32, image [B, 3, H, W] -> [B, 1, H, W] fp32, the bits of
+    ``dep_context_refine(dep_convs, depth, feat, image, "fp16")``.
+
+    Forward: the same ``sfm_dep_context_pack_f16`` and seven
+    ``sfm_conv2_f16`` launches per chunk of ``pairs_per_chunk`` whole pairs;
+    every stage's float16 input is kept, and the last stage runs without its
+    residual so that its ReLU output is kept too (the fp32 "+ depth" is a
+    torch add).  Backward, per chunk in ascending pair order and from the last
+    stage to the first: ``sfm_conv2_wgrad_f16``, ``sfm_conv2_dgrad_f16`` masked
+    by the saved activation (unmasked for the first stage), then
+    ``sfm_dep_context_unpack_grad_f16``, the bilinear upsample's backward.
+
+    Gradients: the seven Conv2d weights (float32, the parameters' layout,
+    added over the chunks in fp32); ``feat`` in its own dtype; ``depth`` the
+    upstream gradient unchanged -- the "+ depth" of PSNet.py:221; the copy of
+    depth inside the cat is detached in the reference and gets nothing;
+    ``image`` none.  The ``feat`` and ``depth`` gradients have the same bits
+    for any chunking.
+
+    Memory: the saved activations are 64 + 128 + 128 + 128 + 96 + 64 + 32 =
+    640 float16 channels, 1280 bytes per full-resolution pixel, for every pair
+    until the backward has run: about 0.6 GB per KITTI pair (376 x 1242);
+    ``max_scratch_bytes`` bounds only the chunk's transient buffers.
+
+    The upstream gradient is cast to float16 before the last stage's
+    backward: a mean loss over a KITTI image's 467 k pixels gives gradients of
+    2e-6 a pixel, below float16's normal range, so train with the GradScaler
+    the reference already uses under MIXED_PREC.
+
+    Refused with a named reason: CPU tensors, a call outside float16 CUDA
+    autocast, a non-stock layout (``dep_stock_layout``), any BatchNorm2d stage
+    (in training mode its batch statistics have no backward here; in eval mode
+    the folded affine has none either), and a weight that is not float32 on
+    the tensors' device."""
+    for t, n in ((depth, "depth"), (feat, "feat"), (image, "image")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise RuntimeError(f"dep_context_refine_autograd needs device tensors (HIP path, no CPU fallback): {n}")
+    if not torch.is_autocast_enabled() or _autocast_gpu_dtype() != torch.float16:
+        raise RuntimeError("dep_context_refine_autograd computes the stack in float16: call it under "
+                           "torch.autocast('cuda', torch.float16)")
+    if depth.dim() != 4 or depth.shape[1] != 1 or depth.dtype != torch.float32:
+        raise RuntimeError("depth must be [B, 1, H, W] float32")
+    B, _, H, W = depth.shape
+    if feat.dim() != 4 or feat.shape[0] != B or feat.shape[1] != 32 or feat.dtype not in _FEAT_DTYPE:
+        raise RuntimeError(f"feat must be [{B}, 32, h, w] float16, bfloat16 or float32")
+    if tuple(image.shape) != (B, 3, H, W) or not image.is_floating_point():
+        raise RuntimeError(f"image must be [{B}, 3, {H}, {W}] floating point")
+    if not dep_stock_layout(dep_convs):
+        _stages(dep_convs)      # raises the named reason, if that is it
+        raise ContextStackError("the refinement stack must take 36 channels and end in one")
+    stages = _stages(dep_convs)
+    for i, (conv, bn, relu) in enumerate(stages):
+        if bn is not None:
+            mode = "in training mode (batch statistics)" if bn.training else "in eval mode (a folded affine)"
+            raise ContextStackError(f"stage {i}: BatchNorm2d {mode} has no backward on the float16 route")
+        if conv.weight.dtype != torch.float32 or conv.weight.device != depth.device:
+            raise ContextStackError(f"stage {i}: the weight must be float32 on the tensors' device")
+    nb_max = pairs_per_chunk(B, H, W, max_scratch_bytes)
+    return _DepContextStack.apply(dep_convs, nb_max, depth, feat, image, *[conv.weight for conv, _, _ in stages])
 
 
 def _autocast_gpu_dtype():

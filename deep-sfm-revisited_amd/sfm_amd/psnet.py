@@ -26,6 +26,8 @@ and runs its forward with the hot path on libsfm_hip:
                       convs under float16 autocast with                sfm_conv2_f16 / sfm_conv2_dgrad_f16 /
                       ``context_grad`` "fp16"                          sfm_conv2_wgrad_f16 (HIP MFMA),
                                                                        sfm_context_pack_f16 / _unpack_grad_f16 (HIP)
+                      dep_convs under float16 autocast with            the same three conv2 kernels,
+                      ``dep_context_grad`` "fp16"                      sfm_dep_context_pack_f16 / _unpack_grad_f16 (HIP)
   dep_convs           full-resolution depth refinement (PSNET_DEP_CONTEXT, 218-225): bilinear upsample + cat
                       sfm_dep_context_pack_* (HIP), the stack      sfm_conv2_* (HIP MFMA) under float16 autocast
                       in eval mode (``dep_context_precision``); else   torch (MIOpen)
@@ -42,7 +44,8 @@ import torch.nn.functional as F
 
 from . import feature as _feature
 from .config import cfg as _default_cfg
-from .context import context_refine, context_refine_autograd, dep_context_refine, dep_stock_layout, stock_layout
+from .context import (context_refine, context_refine_autograd, dep_context_refine, dep_context_refine_autograd,
+                      dep_stock_layout, stock_layout)
 from .depth import depth_head, depth_head_autograd
 from .regularize import CostRegularization, f16_features, fused_channels_last, sweep_regularize_fused
 from .sweep import plane_sweep_cost, plane_sweep_cost_autograd, quarter_intrinsics
@@ -224,15 +227,21 @@ class PSNet(CostRegularization):
     forward and backward on libsfm_hip in float16, at the cost of 1280 bytes
     of saved activations per pixel and plane; needs float16 CUDA autocast at
     the call and raises without it; a stack with BatchNorm2d, cfg.CONTEXT_BN,
-    is refused; profiles/context_bwd_ab.txt).  ``dep_convs`` stays with the
-    modules.
+    is refused; profiles/context_bwd_ab.txt).  ``dep_context_grad`` selects the
+    same for ``dep_convs`` under cfg.PSNET_DEP_CONTEXT: "torch" (default: the
+    float32 F.interpolate + torch.cat and the modules) or "fp16" (opt-in:
+    ``sfm_amd.context.dep_context_refine_autograd``, the upsample, every stage
+    and their backward on libsfm_hip in float16, at the cost of 1280 bytes of
+    saved activations per full-resolution pixel; the same conditions and
+    refusals; profiles/dep_context_bwd_ab.txt).
     Everything else is unchanged bit for bit: calls under ``torch.no_grad()``
     in either mode, and the float16 eval routes, whose HIP features carry no
     grad and so never enter the differentiable route."""
 
     def __init__(self, nlabel, mindepth=None, cfg=None, feature_fn=None, cost_dtype=torch.float32,
                  conv_precision="auto", context_precision="auto", dep_context_precision="auto",
-                 feature_precision="auto", regularize_grad="auto", regularize_norm="torch", context_grad="torch"):
+                 feature_precision="auto", regularize_grad="auto", regularize_norm="torch", context_grad="torch",
+                 dep_context_grad="torch"):
         super().__init__(64)
         c = _default_cfg if cfg is None else cfg
         if c.get("COST_BY_COLOR", False) or c.get("COST_BY_COLOR_WITH_FEAT", False):
@@ -264,6 +273,9 @@ class PSNet(CostRegularization):
         if context_grad not in ("torch", "fp16"):
             raise ValueError(f"unknown context_grad {context_grad!r}")
         self.context_grad = context_grad
+        if dep_context_grad not in ("torch", "fp16"):
+            raise ValueError(f"unknown dep_context_grad {dep_context_grad!r}")
+        self.dep_context_grad = dep_context_grad
         self.feature_extraction = FeatureExtraction() if feature_fn is None else feature_fn
         if c.get("IND_CONTEXT", False):
             self.context_net = FeatureExtraction()
@@ -393,6 +405,19 @@ class PSNet(CostRegularization):
                                "context_grad at 'torch'")
         return p
 
+    def dep_context_grad_route(self, device=None):
+        """How the differentiable route runs ``dep_convs`` at this call:
+        "torch" or "fp16" (see ``dep_context_grad``)."""
+        p = self.dep_context_grad
+        if p == "torch":
+            return p
+        on_gpu = device is not None and torch.device(device).type == "cuda"
+        if not (on_gpu and torch.is_autocast_enabled() and _autocast_gpu_dtype() == torch.float16):
+            raise RuntimeError("dep_context_grad='fp16' computes the refinement stack in float16 on the GPU: call the "
+                               "model on a CUDA device under torch.autocast('cuda', torch.float16), or leave "
+                               "dep_context_grad at 'torch'")
+        return p
+
     def _regularize_modules(self, cost):
         """dres0..4 and classify as PSNet.py:160-165 calls them: the modules themselves, which carry a gradient
         and whose BatchNorm follows self.training (the matrix-core stack folds it and has no backward)."""
@@ -494,6 +519,10 @@ class PSNet(CostRegularization):
         if c.get("PSNET_DEP_CONTEXT", False):
             droute = self._grad_stack_route("dep_context_precision", self.dep_context_route, depth.device) if diff \
                 else self.dep_context_route(depth.device)
+            if diff and self.dep_context_grad_route(depth.device) == "fp16":
+                # the stack with a backward on libsfm_hip; depth goes in attached: the function routes only the
+                # gradient of the "+ depth" residual to it, as the reference's cat of depth.detach() does
+                return depth, dep_context_refine_autograd(self.dep_convs, depth, dep_src, ref)
             if droute in ("fp16", "bf16"):
                 # upsample, cat and the stack on libsfm_hip: the features in the dtype they arrive in, no float32
                 # copy, no full-resolution temporary but the stack's own

@@ -881,6 +881,37 @@ int sfm_dep_context_pack_f16(const float* depth, const void* feat, int feat_dtyp
 int sfm_dep_context_pack_bf16(const float* depth, const void* feat, int feat_dtype, const float* image, int batch,
                               int b0, int nb, int channels, int h, int w, int H, int W, void* out, void* stream);
 
+/* The first stage's data gradient of dep_convs back to the features: the
+ * backward of sfm_dep_context_pack_f16's bilinear upsample (models/PSNet.py:218-221:
+ * up_feat = interpolate(refimg_fea, [H, W], bilinear, align_corners=True)) for
+ * pairs b0 .. b0+nb-1.
+ *   grad_in0  [dev] nb x H x W x 64 float16, 16-byte aligned: the gradient
+ *             sfm_conv2_dgrad_f16(..., act = NULL) writes for the stack's first
+ *             stage.  Channels 1..32 are the upsampled features' gradient;
+ *             channel 0 (the reference feeds depth.detach()) and 33..63 (the
+ *             image and the padding) are ignored;
+ *   grad_feat [dev] batch x channels x h x w float32, channels == 32: pairs
+ *             b0 .. b0+nb-1 are written (not added to), the others left as
+ *             they are.
+ * The exact adjoint of the forward with the forward's own weights: with
+ * sy = (h - 1) / (H - 1) (0 when H == 1), fy = sy y, y0 = min((int)fy, h - 1),
+ * y1 = y0 + (y0 < h - 1), ly1 = fy - y0, ly0 = 1 - ly1 in float64, and the same
+ * in x,
+ *   grad_feat[c][i][j] = sum over y, x of wy(i, y) wx(j, x) grad_in0[y][x][1 + c],
+ *   wy(i, y) = ly0 [y0 == i] + ly1 [y1 == i].
+ * A gather: every source pixel finds the destination rows and columns that read
+ * it by evaluating that index expression (no inverted formula), weights them in
+ * float64 and adds them rows ascending, then columns ascending, in float64,
+ * rounded once to float32.  No float atomics: two calls give the same bits, and
+ * a pair's result depends on that pair alone, so on no chunking.  Any ratio:
+ * H == 1 or W == 1 (every destination on source 0), and H < h, where a source
+ * pixel nothing reads is written as +0.  A zero weight still multiplies its
+ * gradient, as torch's backward does, and nothing is filtered: a non-finite
+ * gradient comes through (a GradScaler sees it).  Profile name
+ * "dep_context_unpack_grad". */
+int sfm_dep_context_unpack_grad_f16(const void* grad_in0, int batch, int b0, int nb, int channels, int h, int w, int H,
+                                    int W, float* grad_feat, void* stream);
+
 /* One Conv2d of PSNet's feature CNN (models/submodule.py:11-15 convbn, 22-44
  * BasicBlock with its downsample and "+= x", 108-184 feature_extraction), its
  * BatchNorm2d folded (eval mode): sfm_conv2_f16 generalised to that layer set,

@@ -11,6 +11,8 @@ libsfm_hip.so (include/sfm_hip.h):
   context  PSNet's per-plane context stack and the full-resolution refinement stack on the matrix cores;
            context_refine_autograd and dep_context_refine_autograd with a float16 backward (data and weight
            gradient of every stage; dep_context_unpack_grad, the bilinear upsample's backward)
+  feature  PSNet's feature CNN on the matrix cores; conv2x_autograd, one Conv2d with a float16
+           backward (conv2x_wgrad_f16 / conv2x_dgrad_f16: strided, 1 x 1 and 320-channel layers)
   depth    correlation cost and the soft-argmin depth head; depth_head_autograd with a gradient into the cost
   synth    seeded synthetic KITTI-shaped inputs
   dist     one-process-per-GPU pair sharding and RCCL metric gather
@@ -20,7 +22,9 @@ from . import _lib  # noqa: F401
 
 __all__ = ["ransac", "sweep", "regularize", "synth", "dist", "config", "validate", "plane_sweep_cost_autograd",
            "inverse_warp_autograd", "depth_head_autograd", "conv3_autograd", "batchnorm3_act_autograd",
-           "context_refine_autograd", "dep_context_refine_autograd", "dep_context_unpack_grad"]
+           "context_refine_autograd", "dep_context_refine_autograd", "dep_context_unpack_grad",
+           "conv2x_autograd", "conv2x_wgrad_f16", "conv2x_dgrad_f16",
+           "pack_dgrad_weights2x", "unpack_wgrad2x"]
 
 
 def __getattr__(name):
@@ -37,4 +41,8 @@ def __getattr__(name):
     if name in ("context_refine_autograd", "dep_context_refine_autograd", "dep_context_unpack_grad"):
         from . import context
         return getattr(context, name)
+    if name in ("conv2x_autograd", "conv2x_wgrad_f16", "conv2x_dgrad_f16",
+                "pack_dgrad_weights2x", "unpack_wgrad2x"):
+        from . import feature
+        return getattr(feature, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

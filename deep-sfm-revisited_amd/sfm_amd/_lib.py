@@ -184,6 +184,14 @@ _SIGS = [
     ("sfm_conv2x_f16", ctypes.c_int,
      [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
       ctypes.c_int, _c_dp, _c_dp, ctypes.c_int, _c_dp, _c_dp, _c_dp]),
+    ("sfm_conv2x_wgrad_f16_workspace_bytes", ctypes.c_size_t,
+     [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    ("sfm_conv2x_wgrad_f16", ctypes.c_int,
+     [_c_dp, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+      ctypes.c_int, _c_dp, _c_dp, ctypes.c_size_t, _c_dp]),
+    ("sfm_conv2x_dgrad_f16", ctypes.c_int,
+     [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+      ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp]),
     ("sfm_image_pack_f16", ctypes.c_int, [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp]),
     ("sfm_avgpool_f16", ctypes.c_int,
      [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp]),

@@ -14,6 +14,13 @@ that residual), four ``sfm_avgpool_f16``, one ``sfm_spp_pack_f16`` (the bilinear
 upsamples and the cat) -- the precision torch computes this network at under
 ``cfg.MIXED_PREC`` autocast (SFMnet.py:164).  There is no PyTorch fallback:
 without libsfm_hip.so or a GPU the call raises.
+
+``conv2x_autograd`` is one raw Conv2d of this layer set with a backward, the
+building block for training the CNN under float16 autocast (the reference
+trains in ``model.train()``, main.py:304): ``sfm_conv2x_f16`` forward,
+``sfm_conv2x_wgrad_f16`` and ``sfm_conv2x_dgrad_f16`` backward
+(csrc/feature_bwd.hip).  The whole CNN on it, between torch's BatchNorm2d, is
+not built yet.
 """
 import ctypes
 import weakref
@@ -358,3 +365,133 @@ def feature_extract(module, image, max_scratch_bytes=1 << 30):
                 part = part.clone()
             out[b0:b0 + nb_max].copy_(_run(packed, part))
     return out.permute(0, 3, 1, 2).contiguous()
+
+
+# --- the CNN's backward in float16 (csrc/feature_bwd.hip) ---------------------------
+def pack_dgrad_weights2x(weight):
+    """The weights that turn a layer's kernel into its data gradient
+    (sfm_conv2x_dgrad_f16): Wd[t][ci][co] = W[co][ci][k^2 - 1 - t] as [k^2,
+    cin_pad, cout_pad] for a Conv2d parameter [cout, cin, k, k], rows beyond
+    cin and columns beyond cout zero.  Pure torch, any device and dtype."""
+    cout, cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
+    wd = weight.new_zeros(k * k, _pad32(cin), _pad32(cout))
+    wd[:, :cin, :cout] = weight.reshape(cout, cin, k * k).flip(2).permute(2, 1, 0)
+    return wd
+
+
+def unpack_wgrad2x(gwp, cout, cin, ksize):
+    """sfm_conv2x_wgrad_f16's [k^2, cout_pad, cin_pad] result in the Conv2d
+    parameter's layout [cout, cin, k, k]; the padded rows and columns are
+    dropped.  Pure torch."""
+    return gwp[:, :cout, :cin].permute(1, 2, 0).reshape(cout, cin, ksize, ksize).contiguous()
+
+
+def _check_layer(ksize, stride, dilation):
+    if ksize not in (1, 3) or stride not in (1, 2):
+        raise RuntimeError("ksize must be 3 or 1 and stride 1 or 2")
+    if not 1 <= int(dilation) <= 16 or (dilation != 1 and (ksize != 3 or stride != 1)):
+        raise RuntimeError("dilation must be 1..16, and 1 for a 1 x 1 or stride 2 conv")
+
+
+def conv2x_wgrad_f16(x, grad_out, ksize=3, stride=1, dilation=1):
+    """sfm_conv2x_wgrad_f16: x [images, hin, win, cin] and grad_out [images,
+    hout, wout, cout], contiguous float16 device tensors -> [ksize^2, cout,
+    cin] float32, reproducible bit for bit."""
+    _check_act(x, "x")
+    _check_act(grad_out, "grad_out")
+    _check_layer(ksize, stride, dilation)
+    n, h, w, cin = x.shape
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    if tuple(grad_out.shape[:3]) != (n, ho, wo):
+        raise RuntimeError(f"grad_out must be [{n}, {ho}, {wo}, cout]")
+    cout = grad_out.shape[3]
+    lib = _lib.load()
+    gw = torch.empty((ksize * ksize, cout, cin), dtype=torch.float32, device=x.device)
+    need = lib.sfm_conv2x_wgrad_f16_workspace_bytes(n, cin, cout, h, w, int(ksize), int(stride))
+    ws = torch.empty(max(16, need), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.sfm_conv2x_wgrad_f16(_lib.ptr(x), _lib.ptr(grad_out), n, cin, cout, h, w, int(ksize), int(stride),
+                                      int(dilation), _lib.ptr(gw), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device))
+        _lib.check(rc, "sfm_conv2x_wgrad_f16")
+    return gw
+
+
+def conv2x_dgrad_f16(grad_out, weights_d, in_hw, ksize=3, stride=1, dilation=1):
+    """sfm_conv2x_dgrad_f16: grad_out [images, hout, wout, cout] float16,
+    weights_d [ksize^2, cin_pad, cout] float16 (``pack_dgrad_weights2x``),
+    in_hw the layer input's (hin, win) -> [images, hin, win, cin_pad]
+    float16."""
+    _check_act(grad_out, "grad_out")
+    _check_layer(ksize, stride, dilation)
+    n, ho, wo, cout = grad_out.shape
+    if not (isinstance(weights_d, torch.Tensor) and weights_d.is_cuda and weights_d.dtype == torch.float16 and
+            weights_d.is_contiguous() and weights_d.dim() == 3 and weights_d.shape[0] == ksize * ksize and
+            weights_d.shape[2] == cout):
+        raise RuntimeError(f"weights_d must be a contiguous float16 device tensor [{ksize * ksize}, cin_pad, {cout}]")
+    cin = weights_d.shape[1]
+    h, w = int(in_hw[0]), int(in_hw[1])
+    out = torch.empty((n, h, w, cin), dtype=torch.float16, device=grad_out.device)
+    with torch.cuda.device(grad_out.device):
+        rc = _lib.load().sfm_conv2x_dgrad_f16(_lib.ptr(grad_out), n, cout, ho, wo, _lib.ptr(weights_d), cin, h, w,
+                                              int(ksize), int(stride), int(dilation), _lib.ptr(out),
+                                              _lib.stream_ptr(grad_out.device))
+        _lib.check(rc, "sfm_conv2x_dgrad_f16")
+    return out
+
+
+_UNIT = {}      # (device, cout_pad) -> (ones, zeros): the unit affine of the raw convolution
+
+
+def _unit_affine(device, n):
+    key = (str(device), n)
+    if key not in _UNIT:
+        _UNIT[key] = (torch.ones(n, dtype=torch.float32, device=device), torch.zeros(n, dtype=torch.float32, device=device))
+    return _UNIT[key]
+
+
+class _Conv2x(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, x, weight, stride, dilation):
+        cout, cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
+        cout_pad, cin_pad = _pad32(cout), _pad32(cin)
+        wp = torch.zeros(k * k, cout_pad, cin_pad, dtype=torch.float16, device=x.device)
+        wp[:, :cout, :cin] = weight.detach().permute(2, 3, 0, 1).reshape(k * k, cout, cin)
+        one, zero = _unit_affine(x.device, cout_pad)
+        fctx.save_for_backward(x, weight)
+        fctx.layer = (k, int(stride), int(dilation))
+        return conv2x_f16(x, wp, one, zero, k, int(stride), int(dilation), relu=False)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, grad):
+        x, weight = fctx.saved_tensors
+        k, stride, dilation = fctx.layer
+        gy = grad.to(torch.float16).contiguous()
+        gx = gw = None
+        if fctx.needs_input_grad[0]:
+            wd = pack_dgrad_weights2x(weight.detach().float()).to(torch.float16).contiguous()
+            gx = conv2x_dgrad_f16(gy, wd, x.shape[1:3], k, stride, dilation)
+        if fctx.needs_input_grad[1]:
+            gwp = conv2x_wgrad_f16(x, gy, k, stride, dilation)
+            gw = unpack_wgrad2x(gwp, weight.shape[0], weight.shape[1], k).to(weight.dtype)
+        return gx, gw, None, None
+
+
+def conv2x_autograd(x, weight, stride=1, dilation=1):
+    """The raw convolution of one layer with a backward on libsfm_hip: x [n, h,
+    w, cin_pad] contiguous float16 on the device, weight the Conv2d parameter
+    [cout, cin, k, k] (k 3 or 1; any float dtype) -> [n, hout, wout, cout_pad]
+    float16, the bits of ``conv2x_f16`` on the packed float16 weights with
+    scale 1, bias 0, no ReLU and no residual.  Backward: ``sfm_conv2x_dgrad_f16``
+    for x and ``sfm_conv2x_wgrad_f16`` for weight, each run only when its input
+    needs a gradient; the weight gradient comes back in the parameter's layout
+    and dtype."""
+    _check_act(x, "x")
+    if not (isinstance(weight, torch.Tensor) and weight.is_cuda and weight.dim() == 4 and weight.is_floating_point() and
+            weight.shape[2] == weight.shape[3] and weight.shape[2] in (1, 3)):
+        raise RuntimeError("weight must be a floating-point device tensor [cout, cin, k, k], k 3 or 1")
+    if _pad32(weight.shape[1]) != x.shape[3]:
+        raise RuntimeError(f"x has {x.shape[3]} channels, the weight's {weight.shape[1]} pad to {_pad32(weight.shape[1])}")
+    _check_layer(int(weight.shape[2]), stride, dilation)
+    return _Conv2x.apply(x, weight, int(stride), int(dilation))
+

@@ -933,6 +933,73 @@ int sfm_conv2x_f16(const void* in, int images, int cin, int hin, int win, const 
                    int stride, int dilation, const float* scale, const float* bias, int relu, const void* residual,
                    void* out, void* stream);
 
+/* Training the feature CNN in float16 (the reference trains under float16
+ * autocast, cfgs/kitti.yml:10 MIXED_PREC, in model.train()): the weight
+ * gradient of one raw Conv2d of sfm_conv2x_f16's layer set (models/submodule.py:11-15
+ * convbn, 22-44 BasicBlock and its downsample, 108-184 feature_extraction), on
+ * v_mfma_f32_32x32x16_f16 with fp32 accumulation:
+ *   grad_weights[tap][co][ci] = sum over image, y, x of
+ *       grad_out[img, y, x, co] in[img, y stride + (kh - pad) dil, x stride + (kw - pad) dil, ci]
+ * (zero outside the image; tap = kh*ksize + kw; pad = 1 at 3 x 3, 0 at 1 x 1).
+ *   in           [dev] images x hin x win x cin float16, cin a multiple of 32
+ *                from 32 to 320: the layer's input, as sfm_conv2x_f16 read it;
+ *   grad_out     [dev] images x hout x wout x cout float16, cout 32, 64, 96 or
+ *                128, hout = (hin - 1) / stride + 1, wout = (win - 1) / stride + 1:
+ *                the gradient of the raw convolution's output;
+ *   ksize 3 or 1; stride 1 or 2; dilation 1..16, and 1 only for ksize 1 or
+ *                stride 2;
+ *   grad_weights [dev] ksize^2 x cout x cin float32, sfm_conv2x_f16's pack layout;
+ *   workspace    [dev] sfm_conv2x_wgrad_f16_workspace_bytes(images, cin, cout,
+ *                hin, win, ksize, stride) bytes, 16-byte aligned: one ksize^2 x
+ *                cout x cin float32 partial sum per accumulating block.
+ * Every pointer 16-byte aligned; grad_weights and workspace overlap neither
+ * each other nor an input.  Refused: hin * win * max(cin, 128) >= 2^31 (32-bit
+ * in-image offsets; offsets across images are 64-bit).  sfm_conv2_wgrad_f16's
+ * scheme: a fixed grid of accumulating blocks walks contiguous ranges of tiles
+ * (4 rows x 64 columns of grad_out), each block writing one partial, and a
+ * second launch adds the partials in block order: no float atomics, so two
+ * calls give the same bits.  The number of blocks is min(tiles, 512), or the
+ * tuning key conv2_wgrad_blocks (launch shape only, read by both functions).
+ * At ksize 3, stride 1, cin <= 128 the call runs sfm_conv2_wgrad_f16 and the
+ * result is its, bit for bit.  Profile name "conv2x_wgrad" (that case is
+ * recorded under "conv2_wgrad" as well). */
+size_t sfm_conv2x_wgrad_f16_workspace_bytes(int images, int cin, int cout, int hin, int win, int ksize, int stride);
+int sfm_conv2x_wgrad_f16(const void* in, const void* grad_out, int images, int cin, int cout, int hin, int win,
+                         int ksize, int stride, int dilation, float* grad_weights, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
+/* The data gradient of the same layer (models/submodule.py:11-15, 22-44,
+ * 108-184).  With W[co][ci][tap] the layer's weights,
+ *   grad_in[img, p, ci] = sum over tap, co and every output pixel q with
+ *       q stride + (tap - pad) dil = p of W[co][ci][tap] grad_out[img, q, co],
+ * accumulated in fp32 and rounded once to float16 (to nearest even).  No mask
+ * and no fused add: on the training route BatchNorm2d sits between a
+ * convolution and its ReLU, and autograd sums the residual fork.
+ *   grad_out [dev] images x hout x wout x cout float16, cout 32, 64, 96 or 128;
+ *   weights  [dev] ksize^2 x cin x cout float16: the dgrad pack
+ *            Wd[t][ci][co] = W[co][ci][ksize^2 - 1 - t], rows beyond the
+ *            layer's cin and columns beyond its cout zero;
+ *   hin, win the input's size: at stride 2 both 2 hout - 1 and 2 hout are
+ *            inputs of hout rows, so hout == (hin - 1) / stride + 1 is
+ *            required, and the same for win;
+ *   grad_in  [dev] images x hin x win x cin float16, cin a multiple of 32 from
+ *            32 to 320, written in one call (at most 128 channels per launch).
+ * ksize, stride and dilation as above.  A gather, no atomics: two calls give
+ * the same bits.  At stride 1 it is sfm_conv2x_f16's implicit GEMM on grad_out
+ * with Wd at the same dilation.  At stride 2 an input pixel of row parity a and
+ * column parity b reads the kernel rows with a + pad - kh even and the kernel
+ * columns with b + pad - kw even: 1, 2, 2 or 4 live taps per parity class at
+ * 3 x 3.  Every pixel of grad_in is written.  At 3 x 3 with pad 1 every input
+ * pixel is read by an output: p odd by tap 2 of q = (p - 1) / 2 <= hout - 1, p
+ * even by tap 1 of q = p / 2, so no pixel is without a term.  At 1 x 1 / stride
+ * 2 the pixels of an odd row or column are read by no output and are written
+ * as +0, their gradient.  At ksize 3, stride 1, cin <= 128 the call runs
+ * sfm_conv2_dgrad_f16(act = NULL) and the result is its, bit for bit.  Every
+ * pointer 16-byte aligned; grad_in overlaps no input; the same size refusal as
+ * above.  Profile name "conv2x_dgrad". */
+int sfm_conv2x_dgrad_f16(const void* grad_out, int images, int cout, int hout, int wout, const void* weights, int cin,
+                         int hin, int win, int ksize, int stride, int dilation, void* grad_in, void* stream);
+
 /* The feature CNN's first input (models/submodule.py:112 firstconv's 3-channel
  * convbn): image [dev] batch x 3 x h x w float32 -> out [dev] batch x h x w x 32
  * float16, channels 0..2 the image (round to nearest even), 3..31 zero.

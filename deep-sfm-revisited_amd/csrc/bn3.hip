@@ -345,12 +345,6 @@ unsigned apply_grid(int64_t items, int most) {
   return (unsigned)(blocks < most ? blocks : most);
 }
 
-bool overlap(const void* a, size_t na, const void* b, size_t nbytes) {
-  if (!a || !b) return false;
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + nbytes && b0 < a0 + na;
-}
-
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 constexpr size_t kStatsBytes = 5 * 32 * sizeof(float);

@@ -60,10 +60,19 @@ struct Tuning {
                                  // sfm_amd.psnet): 1: float16 features go to the fused sweep as they come
                                  // (sfm_plane_sweep_cl_f16); 0: widened to float32 first (sfm_plane_sweep_cl)
   int conv_wgrad_blocks = 0;     // k_conv3_wgrad accumulating blocks (1..4096); 0: by tile count, at most 512
-  int conv2_wgrad_blocks = 0;    // k_conv2_wgrad accumulating blocks (1..4096); 0: by tile count, at most 512
+  int conv2_wgrad_blocks = 0;    // k_conv2_wgrad<NG, KS, STRIDE> (conv2_wgrad.hip) accumulating blocks, for both
+                                 // 2-D weight-gradient entry points (1..4096); 0: by tile count, at most 512
   int bn_blocks = 0;             // k_bn3_stats / k_bn3_bwd_reduce reducing blocks (1..4096); 0: by voxel count, at most 512
 };
 Tuning& tuning();
+
+// whether the byte ranges [a, a + na) and [b, b + nb) share a byte (the entry points' aliasing checks); a null
+// pointer, an optional operand left out, overlaps nothing
+inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
+  if (!a || !b) return false;
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + nb && b0 < a0 + na;
+}
 
 // Uniform integer division by a host-made magic number (the sweep's window
 // decode, the scorer's store rider).

@@ -3,33 +3,10 @@
 // float16 on the gfx950 matrix cores: the three products a training step needs
 // beside the forward (context.hip).
 //
-// k_conv2_wgrad: the weight gradient of one 3x3 / stride 1 / pad = dilation
-// stage,
-//
-//   gW[tap][co][ci] = sum over img, y, x of gy[img, y, x, co] x[img, y + (kh-1) dil, x + (kw-1) dil, ci]
-//
-// a GEMM per tap whose K axis is the pixel axis, the slow axis of both operands.
-// Both tiles are staged in LDS as they lie in memory ([pixel][32 channels],
-// 64-byte rows per 32-channel chunk) and both MFMA operands are read with
-// ds_read_b64_tr_b16 through one address function (tr_frag, as in
-// regularize_bwd.hip), so a tap's column shift kw dil is a row offset of the x
-// image.  Pixels outside the image are staged as zeros; EXEC is all ones at
-// every read.
-//
-// The full result is up to 144 32x32 accumulators, so the grid splits it:
-// blockIdx.y = (kernel row dy, 32-channel chunk of ci, set of NG co groups),
-// NG = 1, 2, 3 for cout_pad 32, 64 | 128, 96.  A wave holds the three kw taps
-// of its NG groups: 3 NG <= 9 accumulators.  A tile is 4 rows x 64 columns of
-// gy; per tile the block stages gy's NG chunks and, as k_conv2 does per kernel
-// row, x's rows y0 + (dy-1) dil + 0..3, columns x0 - dil .. x0 + 63 + dil (a
-// stage whose rows are all outside the image is skipped).  Wave r owns tile row
-// r: per 16-pixel chunk it reads NG gy fragments and 3 x fragments for 3 NG
-// MFMAs (2 (3 + NG) / (3 NG) transposing reads per MFMA: 2.7, 1.7, 1.3).  The
-// grid is a fixed number of blocks; block k walks the contiguous tile range
-// [k T / n, (k + 1) T / n), accumulates in registers, adds its four waves'
-// accumulators through LDS in wave order and writes one partial -- zeros when
-// its range is empty.  k_conv2_wgrad_reduce adds the partials in block order:
-// no float atomics, the same bits from run to run.
+// The weight gradient of a 3x3 / stride 1 / pad = dilation stage is
+// k_conv2_wgrad<NG, 3, 1> (conv2_wgrad.hip), the kernel the feature CNN's
+// layers run too: sfm_conv2_wgrad_f16 checks its arguments and calls that
+// file's launcher.
 //
 // The data gradient is k_conv2 itself (conv2_tile.h) on flipped weights with
 // the MASK epilogue; k_context_unpack_grad carries the first stage's gradient
@@ -38,148 +15,10 @@
 // backward of its pack's bilinear upsample into the features.
 #include <string>
 #include "conv2_tile.h"
+#include "conv2_wgrad.h"
 
 namespace sfm {
 namespace {
-
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kW2TileX = 64;            // gy columns per tile
-constexpr int kW2Rows = 4;              // gy rows per tile: one per wave
-constexpr int kW2Threads = 256;
-constexpr int kW2DefaultBlocks = 512;   // 2 per CU on MI355X (256 CUs)
-constexpr int w2_g_bytes(int ng) { return ng * kW2Rows * kW2TileX * 64; }
-constexpr int w2_x_bytes(int dil) { return kW2Rows * (kW2TileX + 2 * dil) * 64; }
-constexpr int w2_partial(int ng) { return 3 * ng * 32 * 32; }   // floats per block and slice
-constexpr int w2_ng(int cout_pad) { return cout_pad == 96 ? 3 : cout_pad == 32 ? 1 : 2; }
-static_assert(w2_g_bytes(3) + w2_x_bytes(kMaxDil) <= 80 * 1024, "two blocks per CU (160 KB of LDS)");
-static_assert(w2_partial(3) * 4 <= w2_g_bytes(3) && w2_partial(1) * 4 <= w2_g_bytes(1),
-              "the block's reduction image fits the gy stage");
-
-// One 32x32x16 MFMA operand from a [pixel][32 channels] f16 image (64-byte
-// rows): rows = 32 channels, k = 16 consecutive pixels from `pixel0`
-// (regularize_bwd.hip's tr_frag: lane l gets channel l % 32 of pixels pixel0 +
-// 8 (l / 32) + 0..7).
-__device__ __forceinline__ f16x8 tr_frag(const unsigned char* img, int pixel0, int lane) {
-  const int v = pixel0 + 8 * (lane >> 5) + ((lane >> 2) & 3);
-  const unsigned char* a = img + v * 64 + 32 * ((lane >> 4) & 1) + 8 * (lane & 3);
-  typedef short i16x4 __attribute__((vector_size(8)));
-  typedef __attribute__((address_space(3))) i16x4 lds_i16x4;
-  const f16x4 lo = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4*)a));
-  const f16x4 hi = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4*)(a + 4 * 64)));
-  return f16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
-template <int NG>
-__global__ __launch_bounds__(kW2Threads, 2) void k_conv2_wgrad(
-    const unsigned short* __restrict__ x, const unsigned short* __restrict__ gy, int cin, int cop, int dil, int H, int W,
-    int ntx, int nty, int64_t ntiles, float* __restrict__ partial) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  unsigned char* lds_g = lds;
-  unsigned char* lds_x = lds + w2_g_bytes(NG);
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int nci = cin >> 5, nset = (cop >> 5) / NG;
-  int sl = blockIdx.y;                            // slice = (dy * nci + cc) * nset + set
-  const int set = sl % nset;
-  sl /= nset;
-  const int cc = sl % nci, dy = sl / nci;
-  const int nb = gridDim.x;
-  const int64_t t0 = ntiles * blockIdx.x / nb, t1 = ntiles * (blockIdx.x + 1) / nb;
-  const int SW = kW2TileX + 2 * dil;              // staged x columns
-  const int64_t plane = (int64_t)H * W;
-
-  f32x16 acc[3][NG];                              // [kw][co group]
-#pragma unroll
-  for (int a = 0; a < 3; ++a)
-#pragma unroll
-    for (int g = 0; g < NG; ++g)
-      for (int i = 0; i < 16; ++i) acc[a][g][i] = 0.0f;
-
-  for (int64_t t = t0; t < t1; ++t) {             // block-uniform bounds: every barrier is reached by all
-    const int tx = (int)(t % ntx);
-    int64_t rest = t / ntx;
-    const int ty = (int)(rest % nty), img = (int)(rest / nty);
-    const int x0 = tx * kW2TileX, y0 = ty * kW2Rows;
-    const int iy0 = y0 + (dy - 1) * dil;          // x's first staged row
-    if (iy0 >= H || iy0 + kW2Rows <= 0) continue; // zero padding: no contribution (block-uniform)
-    __syncthreads();                              // the previous tile's reads are done
-    {
-      const unsigned short* gp = gy + (int64_t)img * plane * cop + set * NG * 32;
-      for (int i = tid; i < NG * kW2Rows * kW2TileX * 4; i += kW2Threads) {
-        const int c = i & 3, col = (i >> 2) & (kW2TileX - 1), r = (i >> 8) & (kW2Rows - 1), grp = i >> 10;
-        const int gx = x0 + col, gyy = y0 + r;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (gx < W && gyy < H) v = *reinterpret_cast<const uint4*>(gp + ((int64_t)gyy * W + gx) * cop + grp * 32 + c * 8);
-        *reinterpret_cast<uint4*>(lds_g + ((grp * kW2Rows + r) * kW2TileX + col) * 64 + c * 16) = v;
-      }
-      const unsigned short* xp = x + (int64_t)img * plane * cin + cc * 32;
-      for (int i = tid; i < kW2Rows * SW * 4; i += kW2Threads) {
-        const int c = i & 3, p = i >> 2;
-        const int ry = p / SW, px = p - ry * SW;
-        const int gx = x0 - dil + px, gyy = iy0 + ry;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (gx >= 0 && gx < W && gyy >= 0 && gyy < H)
-          v = *reinterpret_cast<const uint4*>(xp + ((int64_t)gyy * W + gx) * cin + c * 8);
-        *reinterpret_cast<uint4*>(lds_x + p * 64 + c * 16) = v;
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < kW2TileX / 16; ++c) {
-      f16x8 gf[NG];
-#pragma unroll
-      for (int g = 0; g < NG; ++g) gf[g] = tr_frag(lds_g + g * (kW2Rows * kW2TileX * 64), wave * kW2TileX + c * 16, lane);
-#pragma unroll
-      for (int kw = 0; kw < 3; ++kw) {            // the last chunk at kw = 2 ends at column 48 + 2 dil + 15 < SW
-        const f16x8 xf = tr_frag(lds_x, wave * SW + c * 16 + kw * dil, lane);
-#pragma unroll
-        for (int g = 0; g < NG; ++g) acc[kw][g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(gf[g], xf, acc[kw][g], 0, 0, 0);
-      }
-    }
-  }
-
-  // The four waves' accumulators added in wave order through LDS, then one partial per block.
-  // D[row = co][col = ci]: the lane holds ci = lane % 32 and co = 8 q + 4 (lane / 32) + j in acc[4 q + j].
-  float* red = reinterpret_cast<float*>(lds);     // [kw][group][32 co][32 ci]
-  const int ci = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int wv = 0; wv < kW2Threads / 64; ++wv) {
-    __syncthreads();                              // the operand reads, then the waves before this one, are done
-    if (wave == wv) {
-#pragma unroll
-      for (int kw = 0; kw < 3; ++kw)
-#pragma unroll
-        for (int g = 0; g < NG; ++g)
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              float* e = red + ((kw * NG + g) * 32 + 8 * q + 4 * h + j) * 32 + ci;
-              *e = wv == 0 ? acc[kw][g][4 * q + j] : *e + acc[kw][g][4 * q + j];
-            }
-    }
-  }
-  __syncthreads();
-  float* out = partial + ((int64_t)blockIdx.y * nb + blockIdx.x) * w2_partial(NG);
-  for (int i = tid; i < w2_partial(NG); i += kW2Threads) out[i] = red[i];
-}
-
-// gW[tap][co][ci] = the partials of blocks 0, 1, ... nb - 1 of the element's slice, added in that order
-__global__ __launch_bounds__(256) void k_conv2_wgrad_reduce(const float* __restrict__ partial, int nb, int cin, int cop,
-                                                            int ng, float* __restrict__ gw) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= 9 * cop * cin) return;
-  const int ci = e % cin, co = (e / cin) % cop, tap = e / (cin * cop);
-  const int dy = tap / 3, kw = tap - dy * 3;
-  const int cog = co >> 5, set = cog / ng, grp = cog - set * ng;
-  const int slice = (dy * (cin >> 5) + (ci >> 5)) * ((cop >> 5) / ng) + set;
-  const int ps = w2_partial(ng);
-  const float* p = partial + (int64_t)slice * nb * ps + ((kw * ng + grp) * 32 + (co & 31)) * 32 + (ci & 31);
-  float s = 0.0f;
-  for (int k = 0; k < nb; ++k) s = s + p[(int64_t)k * ps];
-  gw[e] = s;
-}
 
 // The first stage's data gradient g [batch][nl][h][w][64] (channels 0..31 the
 // features', 32 the plane's, the rest ignored) back to PSNet's tensors.  One
@@ -297,52 +136,6 @@ __global__ __launch_bounds__(256) void k_dep_unpack_grad(const unsigned short* _
   }
 }
 
-struct Wgrad2Plan {
-  int ntx, nty, blocks, ng;
-  int64_t ntiles;
-};
-
-Wgrad2Plan wgrad2_plan(int images, int cout_pad, int h, int w) {
-  Wgrad2Plan p;
-  p.ntx = (w + kW2TileX - 1) / kW2TileX;
-  p.nty = (h + kW2Rows - 1) / kW2Rows;
-  p.ntiles = (int64_t)p.ntx * p.nty * images;
-  p.ng = w2_ng(cout_pad);
-  // conv2_wgrad_blocks: a given number of accumulating blocks (launch shape only; more blocks than tiles is
-  // allowed: the spare ones write zero partials)
-  const int forced = tuning().conv2_wgrad_blocks;
-  p.blocks = forced > 0 ? forced : (int)(p.ntiles < kW2DefaultBlocks ? p.ntiles : kW2DefaultBlocks);
-  return p;
-}
-
-size_t wgrad2_ws_bytes(const Wgrad2Plan& p, int cin, int cout_pad) {
-  return (size_t)p.blocks * 9 * cout_pad * cin * sizeof(float);
-}
-
-bool chan_ok(int c) { return c == 32 || c == 64 || c == 96 || c == 128; }
-
-bool overlap(const void* a, size_t na, const void* b, size_t nbytes) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + nbytes && b0 < a0 + na;
-}
-
-template <int NG>
-int launch_wgrad2(hipStream_t s, const Wgrad2Plan& p, const void* in, const void* grad_out, int cin, int cop, int dil,
-                  int h, int w, void* workspace) {
-  const unsigned lds = (unsigned)(w2_g_bytes(NG) + w2_x_bytes(dil));
-  // > 64 KB of dynamic LDS must be opted into; set on every such launch (cheap, and correct for whichever
-  // device is current and from any host thread, as conv3_lp does)
-  if (lds > 64 * 1024)
-    SFM_HIP(hipFuncSetAttribute((const void*)k_conv2_wgrad<NG>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                w2_g_bytes(NG) + w2_x_bytes(kMaxDil)));
-  const unsigned slices = 3u * (unsigned)(cin / 32) * (unsigned)(cop / 32 / NG);
-  hipLaunchKernelGGL(k_conv2_wgrad<NG>, dim3((unsigned)p.blocks, slices), dim3(kW2Threads), lds, s,
-                     (const unsigned short*)in, (const unsigned short*)grad_out, cin, cop, dil, h, w, p.ntx, p.nty,
-                     p.ntiles, (float*)workspace);
-  SFM_LAUNCHED();
-  return SFM_OK;
-}
-
 }  // namespace
 }  // namespace sfm
 
@@ -352,7 +145,7 @@ extern "C" {
 
 size_t sfm_conv2_wgrad_f16_workspace_bytes(int images, int cin, int cout_pad, int h, int w) {
   if (images < 1 || h < 1 || w < 1 || !chan_ok(cin) || !chan_ok(cout_pad)) return 0;
-  return wgrad2_ws_bytes(wgrad2_plan(images, cout_pad, h, w), cin, cout_pad);
+  return xw_ws_bytes(xw_plan(images, cout_pad, h, w, 3, 1), cin, cout_pad, 3);
 }
 
 int sfm_conv2_wgrad_f16(const void* in, const void* grad_out, int images, int cin, int cout_pad, int h, int w,
@@ -366,8 +159,8 @@ int sfm_conv2_wgrad_f16(const void* in, const void* grad_out, int images, int ci
   SFM_REQUIRE((int64_t)h * w * 128 < ((int64_t)1 << 31), "conv image too large (32-bit in-image offsets)");
   SFM_REQUIRE(((uintptr_t)in & 15) == 0 && ((uintptr_t)grad_out & 15) == 0 && ((uintptr_t)grad_weights & 15) == 0,
               "conv operands must be 16-byte aligned");
-  const Wgrad2Plan p = wgrad2_plan(images, cout_pad, h, w);
-  const size_t need = wgrad2_ws_bytes(p, cin, cout_pad);
+  const XwPlan p = xw_plan(images, cout_pad, h, w, 3, 1);
+  const size_t need = xw_ws_bytes(p, cin, cout_pad, 3);
   if (!workspace || workspace_bytes < need) {
     set_error("conv2 weight-gradient workspace too small: need " + std::to_string(need) + " bytes");
     return SFM_ERR_WORKSPACE;
@@ -384,17 +177,7 @@ int sfm_conv2_wgrad_f16(const void* in, const void* grad_out, int images, int ci
   SFM_REQUIRE(slices <= 65535, "conv weight-gradient grid too large");
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps("conv2_wgrad", s);
-  int rc;
-  switch (p.ng) {
-    case 1: rc = launch_wgrad2<1>(s, p, in, grad_out, cin, cout_pad, dilation, h, w, workspace); break;
-    case 2: rc = launch_wgrad2<2>(s, p, in, grad_out, cin, cout_pad, dilation, h, w, workspace); break;
-    default: rc = launch_wgrad2<3>(s, p, in, grad_out, cin, cout_pad, dilation, h, w, workspace); break;
-  }
-  if (rc != SFM_OK) return rc;
-  hipLaunchKernelGGL(k_conv2_wgrad_reduce, dim3((unsigned)((9 * cout_pad * cin + 255) / 256)), dim3(256), 0, s,
-                     (const float*)workspace, p.blocks, cin, cout_pad, p.ng, grad_weights);
-  SFM_LAUNCHED();
-  return SFM_OK;
+  return launch_conv2_wgrad(s, p, in, grad_out, cin, cout_pad, h, w, 3, 1, dilation, workspace, grad_weights);
 }
 
 int sfm_conv2_dgrad_f16(const void* grad_out, int images, int cout_pad, int h, int w, const void* weights, int cin_pad,

@@ -17,13 +17,12 @@
 #pragma once
 #include "common.h"
 #include "act_cvt.h"
+#include "mfma_frag.h"
 
 namespace sfm {
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kTileX = 64;     // output columns per block
 constexpr int kMaxDil = 16;

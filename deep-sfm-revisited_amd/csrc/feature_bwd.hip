@@ -3,26 +3,13 @@
 // float16 on the gfx950 matrix cores, over sfm_conv2x_f16's layer set (feature.hip):
 // 3 x 3 or 1 x 1, stride 1 or 2, 32..320 input channels.
 //
-// k_conv2x_wgrad<NG, KS, STRIDE>: the weight gradient
-//
-//   gW[tap][co][ci] = sum over img, y, x of gy[img, y, x, co] in[img, y S + (kh - pad) dil, x S + (kw - pad) dil, ci]
-//
-// in k_conv2_wgrad's scheme (context_bwd.hip): a GEMM per tap whose K axis is
-// the pixel axis, both tiles staged in LDS as they lie in memory ([pixel][32
-// channels], 64-byte rows), both MFMA operands read with ds_read_b64_tr_b16
-// (tr_frag), blockIdx.y = (kernel row dy, 32-channel chunk of ci, set of NG co
-// groups), a wave holding the KS kw taps of its NG groups, a fixed grid of
-// accumulating blocks over 4-row x 64-column tiles of gy, one partial per block
-// and k_conv2x_wgrad_reduce adding them in block order: no float atomics.
-// What differs is the x stage.  At stride 1 it is columns x0 - pad dil .. x0 +
-// 63 + pad dil and tap kw reads at row offset kw dil.  At stride 2 consecutive gy
-// pixels read x pixels two apart, which tr_frag's 16-consecutive-pixel K axis
-// cannot do, so a staged row holds x's columns split by parity: positions
-// 0..64 the odd columns 2 (x0 + p) - 1, positions 65..128 the even columns
-// 2 (x0 + p - 65).  Tap kw = 0 (column 2 x - 1) then reads the odd image at
-// x - x0, kw = 2 (column 2 x + 1) the odd image at x - x0 + 1 and kw = 1
-// (column 2 x) the even image at x - x0: three reads at consecutive positions.
-// The 1 x 1 / stride 2 stage holds the even columns alone.
+// The weight gradient is k_conv2_wgrad<NG, KS, STRIDE> (conv2_wgrad.hip), the
+// context stack's kernel; sfm_conv2x_wgrad_f16 checks its arguments and calls
+// that file's launcher.  What this CNN's layers add to it is the stride 2 x
+// stage: consecutive gy pixels read x pixels two apart, which the transposing
+// read's 16-consecutive-pixel K axis cannot do, so a staged row holds x's
+// columns split by parity and the three kw taps read three consecutive
+// positions of the odd, even and odd images.
 //
 // The data gradient is a gather, rounded once to float16:
 //   k_conv2x_dgrad1<NG, KS>  stride 1: k_conv2s' implicit GEMM (feature.hip) on gy
@@ -39,167 +26,10 @@
 // sfm_conv2_dgrad_f16 (context_bwd.hip) and return their bits.
 #include <string>
 #include "conv2_tile.h"
+#include "conv2_wgrad.h"
 
 namespace sfm {
 namespace {
-
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kXwTileX = 64;            // gy columns per tile
-constexpr int kXwRows = 4;              // gy rows per tile: one per wave
-constexpr int kXwThreads = 256;
-constexpr int kXwDefaultBlocks = 512;   // 2 per CU on MI355X (256 CUs)
-constexpr int kXwOdd = kXwTileX + 1;    // stride 2, 3 x 3: staged odd columns; the even ones follow
-constexpr int xw_g_bytes(int ng) { return ng * kXwRows * kXwTileX * 64; }
-constexpr int xw_sw(int ks, int stride, int dil) {
-  return stride == 2 ? (ks == 3 ? kXwOdd + kXwTileX : kXwTileX) : kXwTileX + (ks - 1) * dil;
-}
-constexpr int xw_x_bytes(int ks, int stride, int dil) { return kXwRows * xw_sw(ks, stride, dil) * 64; }
-constexpr int xw_partial(int ks, int ng) { return ks * ng * 32 * 32; }   // floats per block and slice
-// co groups per wave: all of them at 1 x 1 (one tap), k_conv2_wgrad's 1, 2, 3 at 3 x 3 -- but 1 for 96 channels at
-// stride 2, whose x stage is 129 columns wide
-constexpr int xw_ng(int cout, int ks, int stride) {
-  return ks == 1 ? cout / 32 : cout == 32 ? 1 : cout == 96 ? (stride == 2 ? 1 : 3) : 2;
-}
-constexpr int kXwMaxLds = 80 * 1024;
-static_assert(xw_g_bytes(3) + xw_x_bytes(3, 1, kMaxDil) <= kXwMaxLds && xw_g_bytes(2) + xw_x_bytes(3, 2, 1) <= kXwMaxLds &&
-                  xw_g_bytes(4) + xw_x_bytes(1, 2, 1) <= kXwMaxLds,
-              "two blocks per CU (160 KB of LDS)");
-static_assert(xw_partial(3, 3) * 4 <= xw_g_bytes(3) && xw_partial(3, 1) * 4 <= xw_g_bytes(1) &&
-                  xw_partial(1, 4) * 4 <= xw_g_bytes(4),
-              "the block's reduction image fits the gy stage");
-
-// One 32x32x16 MFMA operand from a [pixel][32 channels] f16 image (64-byte rows): rows = 32 channels, k = 16
-// consecutive pixels from `pixel0` (context_bwd.hip's tr_frag).
-__device__ __forceinline__ f16x8 tr_frag(const unsigned char* img, int pixel0, int lane) {
-  const int v = pixel0 + 8 * (lane >> 5) + ((lane >> 2) & 3);
-  const unsigned char* a = img + v * 64 + 32 * ((lane >> 4) & 1) + 8 * (lane & 3);
-  typedef short i16x4 __attribute__((vector_size(8)));
-  typedef __attribute__((address_space(3))) i16x4 lds_i16x4;
-  const f16x4 lo = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4*)a));
-  const f16x4 hi = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4*)(a + 4 * 64)));
-  return f16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
-template <int NG, int KS, int STRIDE>
-__global__ __launch_bounds__(kXwThreads, 2) void k_conv2x_wgrad(
-    const unsigned short* __restrict__ x, const unsigned short* __restrict__ gy, int cin, int cop, int dil, int Hin,
-    int Win, int Hout, int Wout, int ntx, int nty, int64_t ntiles, float* __restrict__ partial) {
-  constexpr int PAD = KS == 3 ? 1 : 0;
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  unsigned char* lds_g = lds;
-  unsigned char* lds_x = lds + xw_g_bytes(NG);
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int nci = cin >> 5, nset = (cop >> 5) / NG;
-  int sl = blockIdx.y;                            // slice = (dy * nci + cc) * nset + set
-  const int set = sl % nset;
-  sl /= nset;
-  const int cc = sl % nci, dy = sl / nci;
-  const int nb = gridDim.x;
-  const int64_t t0 = ntiles * blockIdx.x / nb, t1 = ntiles * (blockIdx.x + 1) / nb;
-  const int SW = xw_sw(KS, STRIDE, dil);          // staged x positions per row
-  const int64_t plane_in = (int64_t)Hin * Win, plane_out = (int64_t)Hout * Wout;
-
-  f32x16 acc[KS][NG];                             // [kw][co group]
-#pragma unroll
-  for (int a = 0; a < KS; ++a)
-#pragma unroll
-    for (int g = 0; g < NG; ++g)
-      for (int i = 0; i < 16; ++i) acc[a][g][i] = 0.0f;
-
-  for (int64_t t = t0; t < t1; ++t) {             // block-uniform bounds: every barrier is reached by all
-    const int tx = (int)(t % ntx);
-    int64_t rest = t / ntx;
-    const int ty = (int)(rest % nty), img = (int)(rest / nty);
-    const int x0 = tx * kXwTileX, y0 = ty * kXwRows;
-    const int iy0 = y0 * STRIDE + (dy - PAD) * dil;   // x's first staged row; row r is iy0 + r STRIDE
-    if (iy0 >= Hin || iy0 + (kXwRows - 1) * STRIDE < 0) continue;   // zero padding: no contribution (block-uniform)
-    __syncthreads();                              // the previous tile's reads are done
-    {
-      const unsigned short* gp = gy + (int64_t)img * plane_out * cop + set * NG * 32;
-      for (int i = tid; i < NG * kXwRows * kXwTileX * 4; i += kXwThreads) {
-        const int c = i & 3, col = (i >> 2) & (kXwTileX - 1), r = (i >> 8) & (kXwRows - 1), grp = i >> 10;
-        const int gx = x0 + col, gyy = y0 + r;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (gx < Wout && gyy < Hout)
-          v = *reinterpret_cast<const uint4*>(gp + ((int64_t)gyy * Wout + gx) * cop + grp * 32 + c * 8);
-        *reinterpret_cast<uint4*>(lds_g + ((grp * kXwRows + r) * kXwTileX + col) * 64 + c * 16) = v;
-      }
-      const unsigned short* xp = x + (int64_t)img * plane_in * cin + cc * 32;
-      for (int i = tid; i < kXwRows * SW * 4; i += kXwThreads) {
-        const int c = i & 3, p = i >> 2;
-        const int ry = p / SW, px = p - ry * SW;
-        int gx;
-        if (STRIDE == 1) gx = x0 - PAD * dil + px;
-        else if (KS == 3) gx = px < kXwOdd ? 2 * (x0 + px) - 1 : 2 * (x0 + px - kXwOdd);
-        else gx = 2 * (x0 + px);
-        const int gyy = iy0 + ry * STRIDE;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (gx >= 0 && gx < Win && gyy >= 0 && gyy < Hin)
-          v = *reinterpret_cast<const uint4*>(xp + ((int64_t)gyy * Win + gx) * cin + c * 8);
-        *reinterpret_cast<uint4*>(lds_x + p * 64 + c * 16) = v;
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < kXwTileX / 16; ++c) {
-      f16x8 gf[NG];
-#pragma unroll
-      for (int g = 0; g < NG; ++g) gf[g] = tr_frag(lds_g + g * (kXwRows * kXwTileX * 64), wave * kXwTileX + c * 16, lane);
-#pragma unroll
-      for (int kw = 0; kw < KS; ++kw) {
-        // stride 1: the last chunk at kw = 2 ends at column 48 + 2 dil + 15 < SW; stride 2: the odd image at 0 or 1
-        // (ends at 64 < 65), the even image from 65 (ends at 128 < SW)
-        const int off = STRIDE == 1 ? kw * dil : KS == 1 ? 0 : kw == 1 ? kXwOdd : kw >> 1;
-        const f16x8 xf = tr_frag(lds_x, wave * SW + c * 16 + off, lane);
-#pragma unroll
-        for (int g = 0; g < NG; ++g) acc[kw][g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(gf[g], xf, acc[kw][g], 0, 0, 0);
-      }
-    }
-  }
-
-  // The four waves' accumulators added in wave order through LDS, then one partial per block.
-  // D[row = co][col = ci]: the lane holds ci = lane % 32 and co = 8 q + 4 (lane / 32) + j in acc[4 q + j].
-  float* red = reinterpret_cast<float*>(lds);     // [kw][group][32 co][32 ci]
-  const int ci = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int wv = 0; wv < kXwThreads / 64; ++wv) {
-    __syncthreads();                              // the operand reads, then the waves before this one, are done
-    if (wave == wv) {
-#pragma unroll
-      for (int kw = 0; kw < KS; ++kw)
-#pragma unroll
-        for (int g = 0; g < NG; ++g)
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              float* e = red + ((kw * NG + g) * 32 + 8 * q + 4 * h + j) * 32 + ci;
-              *e = wv == 0 ? acc[kw][g][4 * q + j] : *e + acc[kw][g][4 * q + j];
-            }
-    }
-  }
-  __syncthreads();
-  float* out = partial + ((int64_t)blockIdx.y * nb + blockIdx.x) * xw_partial(KS, NG);
-  for (int i = tid; i < xw_partial(KS, NG); i += kXwThreads) out[i] = red[i];
-}
-
-// gW[tap][co][ci] = the partials of blocks 0, 1, ... nb - 1 of the element's slice, added in that order
-__global__ __launch_bounds__(256) void k_conv2x_wgrad_reduce(const float* __restrict__ partial, int nb, int cin, int cop,
-                                                             int ks, int ng, float* __restrict__ gw) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= ks * ks * cop * cin) return;
-  const int ci = e % cin, co = (e / cin) % cop, tap = e / (cin * cop);
-  const int dy = tap / ks, kw = tap - dy * ks;
-  const int cog = co >> 5, set = cog / ng, grp = cog - set * ng;
-  const int slice = (dy * (cin >> 5) + (ci >> 5)) * ((cop >> 5) / ng) + set;
-  const int ps = xw_partial(ks, ng);
-  const float* p = partial + (int64_t)slice * nb * ps + ((kw * ng + grp) * 32 + (co & 31)) * 32 + (ci & 31);
-  float s = 0.0f;
-  for (int k = 0; k < nb; ++k) s = s + p[(int64_t)k * ps];
-  gw[e] = s;
-}
 
 // One wave's accumulators of a data-gradient tile rounded to float16: D[row = ci][col = pixel]; the lane holds
 // pixel `pix` and channels co0 + 32 g + 8 q + 4 h + (0..3) in acc[g][4 q .. 4 q + 3]; `cin` is the channel stride.
@@ -387,68 +217,6 @@ __global__ __launch_bounds__(kThreads) void k_conv2x_dgrad2(
   dgrad_store<NG>(acc, out, ((int64_t)img * Hin + py) * Win + px, cin, ci0, h);
 }
 
-struct XwPlan {
-  int hout, wout, ntx, nty, blocks, ng;
-  int64_t ntiles;
-};
-
-XwPlan xw_plan(int images, int cout, int hin, int win, int ksize, int stride) {
-  XwPlan p;
-  p.hout = (hin - 1) / stride + 1;
-  p.wout = (win - 1) / stride + 1;
-  p.ntx = (p.wout + kXwTileX - 1) / kXwTileX;
-  p.nty = (p.hout + kXwRows - 1) / kXwRows;
-  p.ntiles = (int64_t)p.ntx * p.nty * images;
-  p.ng = xw_ng(cout, ksize, stride);
-  // conv2_wgrad_blocks, as sfm_conv2_wgrad_f16 reads it: launch shape only
-  const int forced = tuning().conv2_wgrad_blocks;
-  p.blocks = forced > 0 ? forced : (int)(p.ntiles < kXwDefaultBlocks ? p.ntiles : kXwDefaultBlocks);
-  return p;
-}
-
-size_t xw_ws_bytes(const XwPlan& p, int cin, int cout, int ksize) {
-  return (size_t)p.blocks * ksize * ksize * cout * cin * sizeof(float);
-}
-
-bool cout_ok(int c) { return c == 32 || c == 64 || c == 96 || c == 128; }
-bool cin_ok(int c) { return c >= 32 && c <= 320 && c % 32 == 0; }
-
-bool overlap(const void* a, size_t na, const void* b, size_t nbytes) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + nbytes && b0 < a0 + na;
-}
-
-template <int NG, int KS, int STRIDE>
-int launch_xw(hipStream_t s, const XwPlan& p, const void* in, const void* grad_out, int cin, int cout, int dil, int hin,
-              int win, void* workspace) {
-  const unsigned lds = (unsigned)(xw_g_bytes(NG) + xw_x_bytes(KS, STRIDE, dil));
-  // > 64 KB of dynamic LDS must be opted into; set on every such launch (cheap, and correct for whichever
-  // device is current and from any host thread, as sfm_conv2_wgrad_f16 does)
-  if (lds > 64 * 1024)
-    SFM_HIP(hipFuncSetAttribute((const void*)k_conv2x_wgrad<NG, KS, STRIDE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kXwMaxLds));
-  const unsigned slices = (unsigned)KS * (unsigned)(cin / 32) * (unsigned)(cout / 32 / NG);
-  hipLaunchKernelGGL((k_conv2x_wgrad<NG, KS, STRIDE>), dim3((unsigned)p.blocks, slices), dim3(kXwThreads), lds, s,
-                     (const unsigned short*)in, (const unsigned short*)grad_out, cin, cout, dil, hin, win, p.hout,
-                     p.wout, p.ntx, p.nty, p.ntiles, (float*)workspace);
-  SFM_LAUNCHED();
-  return SFM_OK;
-}
-
-template <int KS, int STRIDE>
-int launch_xw_ng(int ng, hipStream_t s, const XwPlan& p, const void* in, const void* grad_out, int cin, int cout,
-                 int dil, int hin, int win, void* workspace) {
-  switch (ng) {
-    case 1: return launch_xw<1, KS, STRIDE>(s, p, in, grad_out, cin, cout, dil, hin, win, workspace);
-    case 2: return launch_xw<2, KS, STRIDE>(s, p, in, grad_out, cin, cout, dil, hin, win, workspace);
-    case 3: return launch_xw<3, KS, STRIDE>(s, p, in, grad_out, cin, cout, dil, hin, win, workspace);
-    default:
-      if constexpr (KS == 1) return launch_xw<4, KS, STRIDE>(s, p, in, grad_out, cin, cout, dil, hin, win, workspace);
-      set_error("conv weight-gradient: no kernel for this channel grouping");
-      return SFM_ERR_ARG;
-  }
-}
-
 template <int NG, int KS>
 void launch_dg(hipStream_t s, int stride, const void* grad_out, int images, int cout, int hout, int wout,
                const void* weights, int cin, int ci0, int hin, int win, int dil, void* grad_in) {
@@ -479,7 +247,7 @@ void launch_dg_ng(int ng, hipStream_t s, int stride, const void* grad_out, int i
 // the checks both entry points share; 0 or the error code
 int check_layer(int images, int cin, int cout, int hin, int win, int ksize, int stride, int dilation) {
   SFM_REQUIRE(cin_ok(cin), "cin must be a multiple of 32 from 32 to 320");
-  SFM_REQUIRE(cout_ok(cout), "cout must be 32, 64, 96 or 128");
+  SFM_REQUIRE(chan_ok(cout), "cout must be 32, 64, 96 or 128");
   SFM_REQUIRE(ksize == 3 || ksize == 1, "ksize must be 3 or 1");
   SFM_REQUIRE(stride == 1 || stride == 2, "stride must be 1 or 2");
   SFM_REQUIRE(dilation >= 1 && dilation <= kMaxDil, "dilation must be 1..16");
@@ -498,7 +266,7 @@ using namespace sfm;
 extern "C" {
 
 size_t sfm_conv2x_wgrad_f16_workspace_bytes(int images, int cin, int cout, int hin, int win, int ksize, int stride) {
-  if (images < 1 || hin < 1 || win < 1 || !cin_ok(cin) || !cout_ok(cout) || (ksize != 3 && ksize != 1) ||
+  if (images < 1 || hin < 1 || win < 1 || !cin_ok(cin) || !chan_ok(cout) || (ksize != 3 && ksize != 1) ||
       (stride != 1 && stride != 2))
     return 0;
   return xw_ws_bytes(xw_plan(images, cout, hin, win, ksize, stride), cin, cout, ksize);
@@ -528,20 +296,11 @@ int sfm_conv2x_wgrad_f16(const void* in, const void* grad_out, int images, int c
   SFM_REQUIRE(slices <= 65535, "conv weight-gradient grid too large");
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps("conv2x_wgrad", s);
-  // the context stack's layer set: its kernel, its bits
+  // the context stack's layer set goes through its entry point: the same kernel, under its "conv2_wgrad" scope too
   if (ksize == 3 && stride == 1 && cin <= 128)
     return sfm_conv2_wgrad_f16(in, grad_out, images, cin, cout, hin, win, dilation, grad_weights, workspace,
                                workspace_bytes, stream);
-  int rc;
-  if (ksize == 3 && stride == 1) rc = launch_xw_ng<3, 1>(p.ng, s, p, in, grad_out, cin, cout, dilation, hin, win, workspace);
-  else if (ksize == 3) rc = launch_xw_ng<3, 2>(p.ng, s, p, in, grad_out, cin, cout, 1, hin, win, workspace);
-  else if (stride == 2) rc = launch_xw_ng<1, 2>(p.ng, s, p, in, grad_out, cin, cout, 1, hin, win, workspace);
-  else rc = launch_xw_ng<1, 1>(p.ng, s, p, in, grad_out, cin, cout, 1, hin, win, workspace);
-  if (rc != SFM_OK) return rc;
-  hipLaunchKernelGGL(k_conv2x_wgrad_reduce, dim3((unsigned)((ksize * ksize * cout * cin + 255) / 256)), dim3(256), 0, s,
-                     (const float*)workspace, p.blocks, cin, cout, ksize, p.ng, grad_weights);
-  SFM_LAUNCHED();
-  return SFM_OK;
+  return launch_conv2_wgrad(s, p, in, grad_out, cin, cout, hin, win, ksize, stride, dilation, workspace, grad_weights);
 }
 
 int sfm_conv2x_dgrad_f16(const void* grad_out, int images, int cout, int hout, int wout, const void* weights, int cin,

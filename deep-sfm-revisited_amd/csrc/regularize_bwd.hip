@@ -16,7 +16,7 @@
 // rows) and both MFMA operands are read with ds_read_b64_tr_b16, the hardware
 // transpose read: a 16-lane group reads a block of 4 voxels x 16 channels and
 // each lane receives one channel of the four voxels.  A and B are read by the
-// same address function, so the k order of the two operands agrees by
+// same address function (tr_frag, mfma_frag.h), so the k order of the two operands agrees by
 // construction.  A tap's shift is a row offset of the X image (64 dx bytes),
 // so it costs nothing.  Every lane takes part in every read (EXEC all ones):
 // voxels outside the volume are staged as zeros, never masked.
@@ -36,13 +36,10 @@
 // bit from run to run.  cin = 64 runs the two 32-channel halves as grid.y.
 #include <string>
 #include "common.h"
+#include "mfma_frag.h"
 
 namespace sfm {
 namespace {
-
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kWgTileX = 64;                      // gy columns per tile
 constexpr int kWgTileY = 4;                       // gy rows per tile
@@ -54,21 +51,6 @@ constexpr int kWgGyBytes = kWgTileY * kWgTileX * 64;     // 16,384
 constexpr int kWgXBytes = kWgHaloY * kWgHaloX * 64;      // 25,344
 constexpr int kWgPartial = 27 * 32 * 32;          // floats per block and 32-channel half
 constexpr int kWgDefaultBlocks = 512;             // 2 per CU on MI355X (256 CUs)
-
-// One 32x32x16 MFMA operand from a [voxel][32 channels] f16 image (64-byte
-// rows): rows = 32 channels, k = 16 consecutive voxels from `voxel0`.  Lane l
-// gets channel l % 32 of voxels voxel0 + 8 (l / 32) + 0..7.  Per 16-lane group
-// g, lane 4 q + p supplies the address of voxel row q, channels 16 (g & 1) +
-// 4 p .. + 3; the second read is 4 voxel rows on.
-__device__ __forceinline__ f16x8 tr_frag(const unsigned char* img, int voxel0, int lane) {
-  const int v = voxel0 + 8 * (lane >> 5) + ((lane >> 2) & 3);
-  const unsigned char* a = img + v * 64 + 32 * ((lane >> 4) & 1) + 8 * (lane & 3);
-  typedef short i16x4 __attribute__((vector_size(8)));
-  typedef __attribute__((address_space(3))) i16x4 lds_i16x4;
-  const f16x4 lo = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4*)a));
-  const f16x4 hi = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4*)(a + 4 * 64)));
-  return f16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
 
 __global__ __launch_bounds__(kWgThreads, 2) void k_conv3_wgrad(
     const unsigned short* __restrict__ x, const unsigned short* __restrict__ gy, int cin, int B, int D, int H, int W,
@@ -189,11 +171,6 @@ WgradPlan wgrad_plan(int batch, int depth, int h, int w) {
 
 size_t wgrad_ws_bytes(const WgradPlan& p, int cin) {
   return (size_t)(cin / 32) * p.blocks * kWgPartial * sizeof(float);
-}
-
-bool overlap(const void* a, size_t na, const void* b, size_t nbytes) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + nbytes && b0 < a0 + na;
 }
 
 }  // namespace

@@ -36,6 +36,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .feature import pack_dgrad_weights2x, unpack_wgrad2x
 
 _ACT_DTYPE = {"fp16": torch.float16, "bf16": torch.bfloat16}
 _SUFFIX = {"fp16": "f16", "bf16": "bf16"}
@@ -348,17 +349,14 @@ def pack_dgrad_weights2(weight):
     gradient (sfm_conv2_dgrad_f16): Wd[t][ci][co] = W[co][ci][8 - t] as
     [9, cin_pad, cout_pad], rows beyond cin and columns beyond cout zero.
     Pure torch, any device and dtype."""
-    cout, cin = weight.shape[:2]
-    wd = weight.new_zeros(9, _pad32(cin), _pad32(cout))
-    wd[:, :cin, :cout] = weight.reshape(cout, cin, 9).flip(2).permute(2, 1, 0)
-    return wd
+    return pack_dgrad_weights2x(weight)
 
 
 def unpack_wgrad2(gwp, cout, cin):
     """sfm_conv2_wgrad_f16's [9, cout_pad, cin_pad] result in the Conv2d
     parameter's layout [cout, cin, 3, 3]; the padded rows and columns are
     dropped.  Pure torch."""
-    return gwp[:, :cout, :cin].permute(1, 2, 0).reshape(cout, cin, 3, 3).contiguous()
+    return unpack_wgrad2x(gwp, cout, cin, 3)
 
 
 def _f16_cl(t, name):

@@ -190,6 +190,35 @@ def test_bits_of_the_context_kernels_where_the_shapes_overlap(cuda, cin, cout, d
     assert torch.equal(a.view(torch.int16), b.view(torch.int16))
 
 
+@pytest.mark.parametrize("dil", [1, 2])
+@pytest.mark.parametrize("cout", [96, 64], ids=["ng3", "ng2"])
+# two column tiles, the second ragged, two row tiles, the second of one row, a second image; a single pixel
+@pytest.mark.parametrize("shape", [(2, 5, 70), (1, 1, 1)], ids=["2x5x70", "1x1x1"])
+def test_one_weight_gradient_kernel_the_same_bits_per_channel_slice(cuda, shape, cout, dil):
+    """3 x 3 / stride 1 at 160 input channels (past sfm_conv2_wgrad_f16's 128)
+    against sfm_conv2_wgrad_f16 on the channels 0..127 and 128..159: each
+    32-channel slice of ci is accumulated by its own blocks, over the same
+    tile ranges, in the same order, so general float16 data gives the same
+    bits -- no tolerance -- at the default and at 3 accumulating blocks."""
+    from sfm_amd import _lib
+    from sfm_amd.context import conv2_wgrad_f16
+    from sfm_amd.feature import conv2x_wgrad_f16
+    n, h, w = shape
+    g = torch.Generator().manual_seed(160 + cout + dil + h * w)
+    x = torch.randn(n, h, w, 160, generator=g).half().to(cuda)
+    gy = torch.randn(n, h, w, cout, generator=g).half().to(cuda)
+    lo, hi = x[..., :128].contiguous(), x[..., 128:].contiguous()
+    try:
+        for nb in (0, 3):
+            _lib.tune("conv2_wgrad_blocks", nb)
+            whole = conv2x_wgrad_f16(x, gy, 3, 1, dil)
+            assert tuple(whole.shape) == (9, cout, 160) and bool((whole != 0).any())
+            assert torch.equal(whole[:, :, :128], conv2_wgrad_f16(lo, gy, dil)), nb
+            assert torch.equal(whole[:, :, 128:], conv2_wgrad_f16(hi, gy, dil)), nb
+    finally:
+        _lib.tune("conv2_wgrad_blocks", 0)
+
+
 @pytest.mark.parametrize("kd", KINDS, ids=[_kid(kd) for kd in KINDS])
 def test_autograd_forward_bits_and_needs_input_grad(cuda, kd):
     """conv2x_autograd's forward is conv2x_f16 with a unit affine, bit for

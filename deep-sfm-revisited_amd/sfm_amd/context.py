@@ -36,7 +36,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .feature import pack_dgrad_weights2x, unpack_wgrad2x
+from .feature import _fold_stage, _pad32, pack_dgrad_weights2x, unpack_wgrad2x
 
 _ACT_DTYPE = {"fp16": torch.float16, "bf16": torch.bfloat16}
 _SUFFIX = {"fp16": "f16", "bf16": "bf16"}
@@ -46,10 +46,6 @@ MAX_DILATION = 16
 
 class ContextStackError(RuntimeError):
     """The module is not a stack ``sfm_conv2_*`` can run."""
-
-
-def _pad32(n):
-    return (n + 31) // 32 * 32
 
 
 def _conv2(x, weights, scale, bias, dilation, relu, cout, residual, precision):
@@ -169,38 +165,96 @@ def pack_context_stack(convs, device, precision="fp16"):
     hit = _PACKED.get(convs)
     if hit is not None and hit[0] == key:
         return hit[1]
-    wdt = _ACT_DTYPE[precision]
-    packed = []
     with torch.no_grad():
-        for conv, bn, relu in stages:
-            w = conv.weight.detach().float().cpu()                 # [cout, cin, 3, 3]
-            cout, cin = w.shape[:2]
-            cout_pad, cin_pad = _pad32(cout), _pad32(cin)
-            wp = torch.zeros(9, cout_pad, cin_pad, dtype=torch.float32)
-            wp[:, :cout, :cin] = w.permute(2, 3, 0, 1).reshape(9, cout, cin)
-            sc = torch.ones(cout_pad)
-            bi = torch.zeros(cout_pad)
-            if bn is not None:
-                g = torch.ones(cout) if bn.weight is None else bn.weight.detach().float().cpu()
-                b = torch.zeros(cout) if bn.bias is None else bn.bias.detach().float().cpu()
-                scale = g / torch.sqrt(bn.running_var.detach().float().cpu() + bn.eps)
-                sc[:cout] = scale
-                bi[:cout] = b - bn.running_mean.detach().float().cpu() * scale
-            packed.append(dict(w=wp.to(device=device, dtype=wdt).contiguous(), scale=sc.to(device),
-                               bias=bi.to(device), cin=cin, cin_pad=cin_pad, cout=cout, cout_pad=cout_pad,
-                               dilation=int(conv.dilation[0]), relu=relu))
+        packed = [_fold_stage(conv, bn, relu, device, _ACT_DTYPE[precision]) for conv, bn, relu in stages]
     _PACKED[convs] = (key, packed)
     return packed
+
+
+def _stock(convs, cin):
+    try:
+        st = _stages(convs)
+    except ContextStackError:
+        return False
+    return st[0][0].in_channels == cin and st[-1][0].out_channels == 1 and len(st) >= 2
 
 
 def stock_layout(convs):
     """Whether ``convs`` is a stack ``context_refine`` runs: stages the
     kernels take, 33 input channels (32 features + the plane), one output."""
-    try:
-        st = _stages(convs)
-    except ContextStackError:
-        return False
-    return st[0][0].in_channels == 33 and st[-1][0].out_channels == 1 and len(st) >= 2
+    return _stock(convs, 33)
+
+
+def _need_device(who, **tensors):
+    for n, t in tensors.items():
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise RuntimeError(f"{who} needs device tensors (HIP path, no CPU fallback): {n}")
+
+
+def _autocast_gpu_dtype():
+    """torch.get_autocast_gpu_dtype(), by its newer name where torch has it."""
+    if hasattr(torch, "get_autocast_dtype"):
+        return torch.get_autocast_dtype("cuda")
+    return torch.get_autocast_gpu_dtype()
+
+
+def _need_f16_autocast(who):
+    if not torch.is_autocast_enabled() or _autocast_gpu_dtype() != torch.float16:
+        raise RuntimeError(f"{who} computes the stack in float16: call it under torch.autocast('cuda', torch.float16)")
+
+
+def _check_context(who, convs, ctx, costs, autocast=False):
+    """``who``'s refusals in their order: device tensors, float16 autocast
+    (the autograd route), shapes, layout."""
+    _need_device(who, ctx=ctx, costs=costs)
+    if autocast:
+        _need_f16_autocast(who)
+    if costs.dim() != 5 or costs.shape[1] != 1 or costs.dtype != torch.float32:
+        raise RuntimeError("costs must be [B, 1, L, h, w] float32")
+    B, _, L, h, w = costs.shape
+    if ctx.dim() != 4 or tuple(ctx.shape) != (B, 32, h, w) or not ctx.is_floating_point():
+        raise RuntimeError(f"ctx must be [{B}, 32, {h}, {w}] floating point")
+    if not stock_layout(convs):
+        _stages(convs)          # raises the named reason, if that is it
+        raise ContextStackError("the context stack must take 33 channels and end in one")
+
+
+def _trainable(stages, device):
+    """The stages' Conv2d weights, or the reason the float16 route has no
+    backward for them."""
+    for i, (conv, bn, relu) in enumerate(stages):
+        if bn is not None:
+            mode = "in training mode (batch statistics)" if bn.training else "in eval mode (a folded affine)"
+            raise ContextStackError(f"stage {i}: BatchNorm2d {mode} has no backward on the float16 route")
+        if conv.weight.dtype != torch.float32 or conv.weight.device != device:
+            raise ContextStackError(f"stage {i}: the weight must be float32 on the tensors' device")
+    return [conv.weight for conv, _, _ in stages]
+
+
+def _run_stack(conv, packed, x, n, h, w, stream, bufs, last, resid):
+    """The packed stages over one chunk: x [n, h, w, 64] the packed first
+    activation, ``conv`` the precision's ``sfm_conv2_*``.  The last stage
+    writes ``last`` (fp32), with ``resid`` (fp32, or None) added in the same
+    launch.  The stages between write the ping-pong buffers ``bufs`` in turn
+    (x is bufs[0]); with ``bufs`` None each writes a tensor of its own and
+    every stage's input is kept.  Returns the kept inputs."""
+    acts = []
+    for i, lay in enumerate(packed):
+        final = lay["cout"] == 1
+        if bufs is None:
+            acts.append(x)
+        if final:
+            y = last
+        elif bufs is None:
+            y = torch.empty((n, h, w, lay["cout"]), dtype=x.dtype, device=x.device)
+        else:
+            y = bufs[(i + 1) % 2]
+        rc = conv(_lib.ptr(x), n, lay["cin_pad"], h, w, _lib.ptr(lay["w"]), lay["cout"], lay["dilation"],
+                  _lib.ptr(lay["scale"]), _lib.ptr(lay["bias"]), 1 if lay["relu"] else 0,
+                  _lib.ptr(resid) if final else None, _lib.ptr(y), stream)
+        _lib.check(rc, "sfm_conv2")
+        x = y
+    return acts
 
 
 def planes_per_chunk(batch, h, w, nlabel, max_scratch_bytes):
@@ -217,17 +271,8 @@ def context_refine(convs, ctx, costs, precision="fp16", max_scratch_bytes=1 << 3
     ``planes_per_chunk``; the result does not depend on the chunking."""
     if precision not in _ACT_DTYPE:
         raise ValueError(f"unknown context precision {precision!r}")
-    for t, n in ((ctx, "ctx"), (costs, "costs")):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda):
-            raise RuntimeError(f"context_refine needs device tensors (HIP path, no CPU fallback): {n}")
-    if costs.dim() != 5 or costs.shape[1] != 1 or costs.dtype != torch.float32:
-        raise RuntimeError("costs must be [B, 1, L, h, w] float32")
+    _check_context("context_refine", convs, ctx, costs)
     B, _, L, h, w = costs.shape
-    if ctx.dim() != 4 or tuple(ctx.shape) != (B, 32, h, w) or not ctx.is_floating_point():
-        raise RuntimeError(f"ctx must be [{B}, 32, {h}, {w}] floating point")
-    if not stock_layout(convs):
-        _stages(convs)          # raises the named reason, if that is it
-        raise ContextStackError("the context stack must take 33 channels and end in one")
     dev = costs.device
     packed = pack_context_stack(convs, dev, precision)
     adt = _ACT_DTYPE[precision]
@@ -248,15 +293,7 @@ def context_refine(convs, ctx, costs, precision="fp16", max_scratch_bytes=1 << 3
             last = out if whole else torch.empty((B, nl, h, w), dtype=torch.float32, device=dev)
             _lib.check(pack(_lib.ptr(ctx32), _lib.ptr(planes), B, L, l0, nl, 32, h, w, _lib.ptr(bufs[0]), stream),
                        "sfm_context_pack")
-            cur = 0
-            for lay in packed:
-                final = lay["cout"] == 1
-                dst = last if final else bufs[1 - cur]
-                rc = conv(_lib.ptr(bufs[cur]), B * nl, lay["cin_pad"], h, w, _lib.ptr(lay["w"]), lay["cout"],
-                          lay["dilation"], _lib.ptr(lay["scale"]), _lib.ptr(lay["bias"]), 1 if lay["relu"] else 0,
-                          _lib.ptr(resid) if final else None, _lib.ptr(dst), stream)
-                _lib.check(rc, "sfm_conv2")
-                cur = 1 - cur
+            _run_stack(conv, packed, bufs[0], B * nl, h, w, stream, bufs, last, resid)
             if not whole:
                 out[:, l0:l0 + nl].copy_(last)
     return out.view(B, 1, L, h, w)
@@ -270,11 +307,25 @@ def dep_stock_layout(dep_convs):
     """Whether ``dep_convs`` is a stack ``dep_context_refine`` runs: stages
     the kernels take, 36 input channels (depth + 32 features + the image),
     one output."""
-    try:
-        st = _stages(dep_convs)
-    except ContextStackError:
-        return False
-    return st[0][0].in_channels == 36 and st[-1][0].out_channels == 1 and len(st) >= 2
+    return _stock(dep_convs, 36)
+
+
+def _check_dep_context(who, dep_convs, depth, feat, image, autocast=False):
+    """``who``'s refusals in their order: device tensors, float16 autocast
+    (the autograd route), shapes, layout."""
+    _need_device(who, depth=depth, feat=feat, image=image)
+    if autocast:
+        _need_f16_autocast(who)
+    if depth.dim() != 4 or depth.shape[1] != 1 or depth.dtype != torch.float32:
+        raise RuntimeError("depth must be [B, 1, H, W] float32")
+    B, _, H, W = depth.shape
+    if feat.dim() != 4 or feat.shape[0] != B or feat.shape[1] != 32 or feat.dtype not in _FEAT_DTYPE:
+        raise RuntimeError(f"feat must be [{B}, 32, h, w] float16, bfloat16 or float32")
+    if tuple(image.shape) != (B, 3, H, W) or not image.is_floating_point():
+        raise RuntimeError(f"image must be [{B}, 3, {H}, {W}] floating point")
+    if not dep_stock_layout(dep_convs):
+        _stages(dep_convs)      # raises the named reason, if that is it
+        raise ContextStackError("the refinement stack must take 36 channels and end in one")
 
 
 def pairs_per_chunk(batch, H, W, max_scratch_bytes):
@@ -294,19 +345,8 @@ def dep_context_refine(dep_convs, depth, feat, image, precision="fp16", max_scra
     chunking.  No PyTorch fallback: CPU tensors raise."""
     if precision not in _ACT_DTYPE:
         raise ValueError(f"unknown context precision {precision!r}")
-    for t, n in ((depth, "depth"), (feat, "feat"), (image, "image")):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda):
-            raise RuntimeError(f"dep_context_refine needs device tensors (HIP path, no CPU fallback): {n}")
-    if depth.dim() != 4 or depth.shape[1] != 1 or depth.dtype != torch.float32:
-        raise RuntimeError("depth must be [B, 1, H, W] float32")
+    _check_dep_context("dep_context_refine", dep_convs, depth, feat, image)
     B, _, H, W = depth.shape
-    if feat.dim() != 4 or feat.shape[0] != B or feat.shape[1] != 32 or feat.dtype not in _FEAT_DTYPE:
-        raise RuntimeError(f"feat must be [{B}, 32, h, w] float16, bfloat16 or float32")
-    if tuple(image.shape) != (B, 3, H, W) or not image.is_floating_point():
-        raise RuntimeError(f"image must be [{B}, 3, {H}, {W}] floating point")
-    if not dep_stock_layout(dep_convs):
-        _stages(dep_convs)      # raises the named reason, if that is it
-        raise ContextStackError("the refinement stack must take 36 channels and end in one")
     h, w = feat.shape[2:]
     dev = depth.device
     packed = pack_context_stack(dep_convs, dev, precision)
@@ -329,15 +369,7 @@ def dep_context_refine(dep_convs, depth, feat, image, precision="fp16", max_scra
             last = out if whole else torch.empty((nb, H, W), dtype=torch.float32, device=dev)
             _lib.check(pack(_lib.ptr(depth), _lib.ptr(feat), _FEAT_DTYPE[feat.dtype], _lib.ptr(image), B, b0, nb, 32,
                             h, w, H, W, _lib.ptr(bufs[0]), stream), "sfm_dep_context_pack")
-            cur = 0
-            for lay in packed:
-                final = lay["cout"] == 1
-                dst = last if final else bufs[1 - cur]
-                rc = conv(_lib.ptr(bufs[cur]), nb, lay["cin_pad"], H, W, _lib.ptr(lay["w"]), lay["cout"],
-                          lay["dilation"], _lib.ptr(lay["scale"]), _lib.ptr(lay["bias"]), 1 if lay["relu"] else 0,
-                          _lib.ptr(depth[b0:b0 + nb]) if final else None, _lib.ptr(dst), stream)
-                _lib.check(rc, "sfm_conv2")
-                cur = 1 - cur
+            _run_stack(conv, packed, bufs[0], nb, H, W, stream, bufs, last, depth[b0:b0 + nb])
             if not whole:
                 out[b0:b0 + nb, 0].copy_(last)
     return out
@@ -436,6 +468,27 @@ def context_unpack_grad(g0, grad_out, l0, first, grad_ctx, grad_planes):
         _lib.check(rc, "sfm_context_unpack_grad_f16")
 
 
+def _stack_backward(acts, grad, relu_out, meta, wds, gws):
+    """One chunk's backward through the stages, last to first: ``acts`` the
+    kept stage inputs [n, h, w, c] float16, ``grad`` and ``relu_out`` the
+    chunk's n h w upstream gradients and last-stage outputs (fp32, one shape),
+    ``wds`` the packed data-gradient weights.  Every stage's weight gradient is
+    added to ``gws`` in fp32 (call in ascending chunk order); returns the first
+    stage's data gradient [n, h, w, 64] float16."""
+    n, h, w = acts[0].shape[:3]
+    # the last stage: through its ReLU, as channel 0 of a zero-padded 32-channel tensor
+    if meta[-1][3]:
+        grad = torch.where(relu_out > 0, grad, torch.zeros_like(grad))
+    g = torch.zeros((n, h, w, 32), dtype=torch.float16, device=grad.device)
+    g[..., 0] = grad.reshape(n, h, w)
+    for s in range(len(meta) - 1, -1, -1):
+        dil = meta[s][2]
+        gw = conv2_wgrad_f16(acts[s], g, dil)
+        gws[s] = gw if gws[s] is None else gws[s] + gw
+        g = conv2_dgrad_f16(g, wds[s], dil, acts[s] if s > 0 else None)        # stage 0's input has no ReLU
+    return g
+
+
 class _ContextStack(torch.autograd.Function):
     @staticmethod
     def forward(fctx, convs, nl_max, ctx, costs, *weights):
@@ -454,21 +507,11 @@ class _ContextStack(torch.autograd.Function):
                 x = torch.empty((B * nl, h, w, 64), dtype=torch.float16, device=dev)
                 _lib.check(lib.sfm_context_pack_f16(_lib.ptr(ctx32), _lib.ptr(planes), B, L, l0, nl, 32, h, w,
                                                     _lib.ptr(x), stream), "sfm_context_pack")
-                acts = []
-                for lay in packed:
-                    acts.append(x)
-                    final = lay["cout"] == 1
-                    # the last stage without its residual, so that its ReLU output is kept; the fp32 "+ plane"
-                    # below gives the bits of the fused form
-                    y = torch.empty((B, nl, h, w), dtype=torch.float32, device=dev) if final else \
-                        torch.empty((B * nl, h, w, lay["cout"]), dtype=torch.float16, device=dev)
-                    rc = lib.sfm_conv2_f16(_lib.ptr(x), B * nl, lay["cin_pad"], h, w, _lib.ptr(lay["w"]), lay["cout"],
-                                           lay["dilation"], _lib.ptr(lay["scale"]), _lib.ptr(lay["bias"]),
-                                           1 if lay["relu"] else 0, None, _lib.ptr(y), stream)
-                    _lib.check(rc, "sfm_conv2")
-                    x = y
-                relu_out[:, l0:l0 + nl].copy_(x)
-                saved.append(acts)
+                # the last stage without its residual, so that its ReLU output is kept; the fp32 "+ plane"
+                # below gives the bits of the fused form
+                last = torch.empty((B, nl, h, w), dtype=torch.float32, device=dev)
+                saved.append(_run_stack(lib.sfm_conv2_f16, packed, x, B * nl, h, w, stream, None, last, None))
+                relu_out[:, l0:l0 + nl].copy_(last)
         fctx.saved, fctx.relu_out, fctx.nl_max = saved, relu_out, nl_max
         fctx.meta = [(lay["cin"], lay["cout"], lay["dilation"], lay["relu"]) for lay in packed]
         fctx.ctx_dtype = ctx.dtype
@@ -489,18 +532,7 @@ class _ContextStack(torch.autograd.Function):
         grad_planes = torch.empty((B, L, h, w), dtype=torch.float32, device=dev)
         for k, l0 in enumerate(range(0, L, nl_max)):        # ascending: the unpack kernel's summation order
             nl = min(nl_max, L - l0)
-            acts = fctx.saved[k]
-            # the last stage: through its ReLU, as channel 0 of a zero-padded 32-channel tensor
-            gl = go[:, l0:l0 + nl]
-            if meta[-1][3]:
-                gl = torch.where(fctx.relu_out[:, l0:l0 + nl] > 0, gl, torch.zeros_like(gl))
-            g = torch.zeros((B * nl, h, w, 32), dtype=torch.float16, device=dev)
-            g[..., 0] = gl.reshape(B * nl, h, w)
-            for s in range(len(meta) - 1, -1, -1):
-                dil = meta[s][2]
-                gw = conv2_wgrad_f16(acts[s], g, dil)
-                gws[s] = gw if gws[s] is None else gws[s] + gw
-                g = conv2_dgrad_f16(g, wds[s], dil, acts[s] if s > 0 else None)
+            g = _stack_backward(fctx.saved[k], go[:, l0:l0 + nl], fctx.relu_out[:, l0:l0 + nl], meta, wds, gws)
             context_unpack_grad(g.view(B, nl, h, w, 64), go, l0, k == 0, grad_ctx, grad_planes)
             fctx.saved[k] = None                            # a chunk's activations are done with
         out_w = [unpack_wgrad2(gw, m[1], m[0]).to(wt.dtype) for gw, m, wt in zip(gws, meta, weights)]
@@ -533,29 +565,11 @@ def context_refine_autograd(convs, ctx, costs, max_scratch_bytes=1 << 30):
     autocast, a non-stock layout, and any BatchNorm2d stage (in training mode
     its batch statistics have no backward here; in eval mode the folded affine
     has none either)."""
-    for t, n in ((ctx, "ctx"), (costs, "costs")):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda):
-            raise RuntimeError(f"context_refine_autograd needs device tensors (HIP path, no CPU fallback): {n}")
-    if not torch.is_autocast_enabled() or _autocast_gpu_dtype() != torch.float16:
-        raise RuntimeError("context_refine_autograd computes the stack in float16: call it under "
-                           "torch.autocast('cuda', torch.float16)")
-    if costs.dim() != 5 or costs.shape[1] != 1 or costs.dtype != torch.float32:
-        raise RuntimeError("costs must be [B, 1, L, h, w] float32")
+    _check_context("context_refine_autograd", convs, ctx, costs, autocast=True)
+    weights = _trainable(_stages(convs), costs.device)
     B, _, L, h, w = costs.shape
-    if ctx.dim() != 4 or tuple(ctx.shape) != (B, 32, h, w) or not ctx.is_floating_point():
-        raise RuntimeError(f"ctx must be [{B}, 32, {h}, {w}] floating point")
-    if not stock_layout(convs):
-        _stages(convs)          # raises the named reason, if that is it
-        raise ContextStackError("the context stack must take 33 channels and end in one")
-    stages = _stages(convs)
-    for i, (conv, bn, relu) in enumerate(stages):
-        if bn is not None:
-            mode = "in training mode (batch statistics)" if bn.training else "in eval mode (a folded affine)"
-            raise ContextStackError(f"stage {i}: BatchNorm2d {mode} has no backward on the float16 route")
-        if conv.weight.dtype != torch.float32 or conv.weight.device != costs.device:
-            raise ContextStackError(f"stage {i}: the weight must be float32 on the tensors' device")
     nl_max = planes_per_chunk(B, h, w, L, max_scratch_bytes)
-    return _ContextStack.apply(convs, nl_max, ctx, costs, *[conv.weight for conv, _, _ in stages])
+    return _ContextStack.apply(convs, nl_max, ctx, costs, *weights)
 
 
 # --- dep_convs' backward in float16 (csrc/context_bwd.hip) --------------------------
@@ -601,24 +615,12 @@ class _DepContextStack(torch.autograd.Function):
                 _lib.check(lib.sfm_dep_context_pack_f16(_lib.ptr(depth32), _lib.ptr(feat_c), _FEAT_DTYPE[feat_c.dtype],
                                                         _lib.ptr(image32), B, b0, nb, 32, h, w, H, W, _lib.ptr(x),
                                                         stream), "sfm_dep_context_pack")
-                acts = []
-                for lay in packed:
-                    acts.append(x)
-                    final = lay["cout"] == 1
-                    # the last stage without its residual, so that its ReLU output is kept; the fp32 "+ depth"
-                    # below gives the bits of the fused form.  A chunk writes a buffer of its own, 16-byte aligned.
-                    if final:
-                        y = relu_out if nb == B else torch.empty((nb, 1, H, W), dtype=torch.float32, device=dev)
-                    else:
-                        y = torch.empty((nb, H, W, lay["cout"]), dtype=torch.float16, device=dev)
-                    rc = lib.sfm_conv2_f16(_lib.ptr(x), nb, lay["cin_pad"], H, W, _lib.ptr(lay["w"]), lay["cout"],
-                                           lay["dilation"], _lib.ptr(lay["scale"]), _lib.ptr(lay["bias"]),
-                                           1 if lay["relu"] else 0, None, _lib.ptr(y), stream)
-                    _lib.check(rc, "sfm_conv2")
-                    x = y
+                # the last stage without its residual, so that its ReLU output is kept; the fp32 "+ depth"
+                # below gives the bits of the fused form.  A chunk writes a buffer of its own, 16-byte aligned.
+                last = relu_out if nb == B else torch.empty((nb, 1, H, W), dtype=torch.float32, device=dev)
+                saved.append(_run_stack(lib.sfm_conv2_f16, packed, x, nb, H, W, stream, None, last, None))
                 if nb != B:
-                    relu_out[b0:b0 + nb].copy_(x)
-                saved.append(acts)
+                    relu_out[b0:b0 + nb].copy_(last)
         fctx.saved, fctx.relu_out, fctx.nb_max = saved, relu_out, nb_max
         fctx.meta = [(lay["cin"], lay["cout"], lay["dilation"], lay["relu"]) for lay in packed]
         fctx.feat_shape, fctx.feat_dtype = tuple(feat.shape), feat.dtype
@@ -638,18 +640,7 @@ class _DepContextStack(torch.autograd.Function):
         grad_feat = torch.empty(fctx.feat_shape, dtype=torch.float32, device=dev)
         for k, b0 in enumerate(range(0, B, nb_max)):        # ascending pair order
             nb = min(nb_max, B - b0)
-            acts = fctx.saved[k]
-            # the last stage: through its ReLU, as channel 0 of a zero-padded 32-channel tensor
-            gl = go[b0:b0 + nb, 0]
-            if meta[-1][3]:
-                gl = torch.where(fctx.relu_out[b0:b0 + nb, 0] > 0, gl, torch.zeros_like(gl))
-            g = torch.zeros((nb, H, W, 32), dtype=torch.float16, device=dev)
-            g[..., 0] = gl
-            for s in range(len(meta) - 1, -1, -1):
-                dil = meta[s][2]
-                gw = conv2_wgrad_f16(acts[s], g, dil)
-                gws[s] = gw if gws[s] is None else gws[s] + gw
-                g = conv2_dgrad_f16(g, wds[s], dil, acts[s] if s > 0 else None)
+            g = _stack_backward(fctx.saved[k], go[b0:b0 + nb, 0], fctx.relu_out[b0:b0 + nb, 0], meta, wds, gws)
             dep_context_unpack_grad(g, b0, grad_feat)
             fctx.saved[k] = None                            # a chunk's activations are done with
         out_w = [unpack_wgrad2(gw, m[1], m[0]).to(wt.dtype) for gw, m, wt in zip(gws, meta, weights)]
@@ -695,35 +686,8 @@ def dep_context_refine_autograd(dep_convs, depth, feat, image, max_scratch_bytes
     (in training mode its batch statistics have no backward here; in eval mode
     the folded affine has none either), and a weight that is not float32 on
     the tensors' device."""
-    for t, n in ((depth, "depth"), (feat, "feat"), (image, "image")):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda):
-            raise RuntimeError(f"dep_context_refine_autograd needs device tensors (HIP path, no CPU fallback): {n}")
-    if not torch.is_autocast_enabled() or _autocast_gpu_dtype() != torch.float16:
-        raise RuntimeError("dep_context_refine_autograd computes the stack in float16: call it under "
-                           "torch.autocast('cuda', torch.float16)")
-    if depth.dim() != 4 or depth.shape[1] != 1 or depth.dtype != torch.float32:
-        raise RuntimeError("depth must be [B, 1, H, W] float32")
+    _check_dep_context("dep_context_refine_autograd", dep_convs, depth, feat, image, autocast=True)
+    weights = _trainable(_stages(dep_convs), depth.device)
     B, _, H, W = depth.shape
-    if feat.dim() != 4 or feat.shape[0] != B or feat.shape[1] != 32 or feat.dtype not in _FEAT_DTYPE:
-        raise RuntimeError(f"feat must be [{B}, 32, h, w] float16, bfloat16 or float32")
-    if tuple(image.shape) != (B, 3, H, W) or not image.is_floating_point():
-        raise RuntimeError(f"image must be [{B}, 3, {H}, {W}] floating point")
-    if not dep_stock_layout(dep_convs):
-        _stages(dep_convs)      # raises the named reason, if that is it
-        raise ContextStackError("the refinement stack must take 36 channels and end in one")
-    stages = _stages(dep_convs)
-    for i, (conv, bn, relu) in enumerate(stages):
-        if bn is not None:
-            mode = "in training mode (batch statistics)" if bn.training else "in eval mode (a folded affine)"
-            raise ContextStackError(f"stage {i}: BatchNorm2d {mode} has no backward on the float16 route")
-        if conv.weight.dtype != torch.float32 or conv.weight.device != depth.device:
-            raise ContextStackError(f"stage {i}: the weight must be float32 on the tensors' device")
     nb_max = pairs_per_chunk(B, H, W, max_scratch_bytes)
-    return _DepContextStack.apply(dep_convs, nb_max, depth, feat, image, *[conv.weight for conv, _, _ in stages])
-
-
-def _autocast_gpu_dtype():
-    """torch.get_autocast_gpu_dtype(), by its newer name where torch has it."""
-    if hasattr(torch, "get_autocast_dtype"):
-        return torch.get_autocast_dtype("cuda")
-    return torch.get_autocast_gpu_dtype()
+    return _DepContextStack.apply(dep_convs, nb_max, depth, feat, image, *weights)

@@ -158,13 +158,25 @@ def _pad32(n):
     return (n + 31) // 32 * 32
 
 
-def _pack_stage(stage, device):
-    conv, bn, relu = stage
+def pack_weights2x(weight, dtype=None):
+    """A Conv2d parameter [cout, cin, k, k] as the kernels read it: [k^2,
+    cout_pad, cin_pad] (tap = kh*k + kw), rows beyond cout and columns beyond
+    cin zero, in ``dtype`` (the parameter's own by default; the values are
+    rounded to nearest even on the way in).  Pure torch, any device."""
+    cout, cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
+    wp = weight.new_zeros(k * k, _pad32(cout), _pad32(cin), dtype=dtype)
+    wp[:, :cout, :cin] = weight.permute(2, 3, 0, 1).reshape(k * k, cout, cin)
+    return wp
+
+
+def _fold_stage(conv, bn, relu, device, dtype):
+    """One stage as a launch reads it: the packed weight in ``dtype`` and the
+    fp32 scale / bias [cout_pad] of BatchNorm2d folded with its running
+    statistics (eval mode), 1 / 0 without one.  Computed in float32 on the
+    CPU, then moved to ``device``."""
     w = conv.weight.detach().float().cpu()                         # [cout, cin, k, k]
     cout, cin, k = w.shape[0], w.shape[1], w.shape[2]
     cout_pad, cin_pad = _pad32(cout), _pad32(cin)
-    wp = torch.zeros(k * k, cout_pad, cin_pad, dtype=torch.float32)
-    wp[:, :cout, :cin] = w.permute(2, 3, 0, 1).reshape(k * k, cout, cin)
     sc, bi = torch.ones(cout_pad), torch.zeros(cout_pad)
     if bn is not None:
         g = torch.ones(cout) if bn.weight is None else bn.weight.detach().float().cpu()
@@ -172,7 +184,7 @@ def _pack_stage(stage, device):
         scale = g / torch.sqrt(bn.running_var.detach().float().cpu() + bn.eps)
         sc[:cout] = scale
         bi[:cout] = b - bn.running_mean.detach().float().cpu() * scale
-    return dict(w=wp.to(device=device, dtype=torch.float16).contiguous(), scale=sc.to(device), bias=bi.to(device),
+    return dict(w=pack_weights2x(w, dtype).to(device), scale=sc.to(device), bias=bi.to(device),
                 cin=cin, cin_pad=cin_pad, cout=cout, cout_pad=cout_pad, ksize=k, stride=int(conv.stride[0]),
                 dilation=int(conv.dilation[0]), relu=relu)
 
@@ -192,13 +204,15 @@ def pack_feature_extraction(module, device):
     hit = _PACKED.get(module)
     if hit is not None and hit[0] == key:
         return hit[1]
+
+    def fold(stage):
+        return _fold_stage(*stage, device, torch.float16)
     with torch.no_grad():
         packed = dict(
-            first=[_pack_stage(s, device) for s in plan["first"]],
-            layers=[[tuple(None if s is None else _pack_stage(s, device) for s in blk) for blk in blks]
-                    for blks in plan["layers"]],
-            branches=[(p, _pack_stage(s, device)) for p, s in plan["branches"]],
-            last=[_pack_stage(s, device) for s in plan["last"]])
+            first=[fold(s) for s in plan["first"]],
+            layers=[[tuple(None if s is None else fold(s) for s in blk) for blk in blks] for blks in plan["layers"]],
+            branches=[(p, fold(s)) for p, s in plan["branches"]],
+            last=[fold(s) for s in plan["last"]])
     _PACKED[module] = (key, packed)
     return packed
 
@@ -452,11 +466,9 @@ def _unit_affine(device, n):
 class _Conv2x(torch.autograd.Function):
     @staticmethod
     def forward(fctx, x, weight, stride, dilation):
-        cout, cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
-        cout_pad, cin_pad = _pad32(cout), _pad32(cin)
-        wp = torch.zeros(k * k, cout_pad, cin_pad, dtype=torch.float16, device=x.device)
-        wp[:, :cout, :cin] = weight.detach().permute(2, 3, 0, 1).reshape(k * k, cout, cin)
-        one, zero = _unit_affine(x.device, cout_pad)
+        k = weight.shape[2]
+        wp = pack_weights2x(weight.detach(), torch.float16)
+        one, zero = _unit_affine(x.device, wp.shape[1])
         fctx.save_for_backward(x, weight)
         fctx.layer = (k, int(stride), int(dilation))
         return conv2x_f16(x, wp, one, zero, k, int(stride), int(dilation), relu=False)

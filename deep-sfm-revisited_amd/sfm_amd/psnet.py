@@ -44,8 +44,8 @@ import torch.nn.functional as F
 
 from . import feature as _feature
 from .config import cfg as _default_cfg
-from .context import (context_refine, context_refine_autograd, dep_context_refine, dep_context_refine_autograd,
-                      dep_stock_layout, stock_layout)
+from .context import (_autocast_gpu_dtype, context_refine, context_refine_autograd, dep_context_refine,
+                      dep_context_refine_autograd, dep_stock_layout, stock_layout)
 from .depth import depth_head, depth_head_autograd
 from .regularize import CostRegularization, f16_features, fused_channels_last, sweep_regularize_fused
 from .sweep import plane_sweep_cost, plane_sweep_cost_autograd, quarter_intrinsics
@@ -78,13 +78,6 @@ def torch_depth_head(cost, nlabel, min_depth, out_hw, predict_by_depth=False, sc
         mul = float(min_depth) if scale is None else float(scale)
         return torch.sum(prob * (idx * float(int(min_depth))), 1, keepdim=True) * mul
     return float(min_depth) * L / (torch.sum(prob * idx, 1, keepdim=True) + 1e-16)
-
-
-def _autocast_gpu_dtype():
-    """torch.get_autocast_gpu_dtype(), by its newer name where torch has it."""
-    if hasattr(torch, "get_autocast_dtype"):
-        return torch.get_autocast_dtype("cuda")
-    return torch.get_autocast_gpu_dtype()
 
 
 def _conv_bn(cin, cout, k, stride, pad, dilation):

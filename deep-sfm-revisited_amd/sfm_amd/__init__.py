@@ -12,7 +12,9 @@ libsfm_hip.so (include/sfm_hip.h):
            context_refine_autograd and dep_context_refine_autograd with a float16 backward (data and weight
            gradient of every stage; dep_context_unpack_grad, the bilinear upsample's backward)
   feature  PSNet's feature CNN on the matrix cores; conv2x_autograd, one Conv2d with a float16
-           backward (conv2x_wgrad_f16 / conv2x_dgrad_f16: strided, 1 x 1 and 320-channel layers)
+           backward (conv2x_wgrad_f16 / conv2x_dgrad_f16: strided, 1 x 1 and 320-channel layers);
+           batchnorm2_act_autograd (BatchNorm2d + ReLU + residual in float16, forward and backward),
+           convbn2_autograd and basic_block_autograd (one convbn, one BasicBlock) on them
   depth    correlation cost and the soft-argmin depth head; depth_head_autograd with a gradient into the cost
   synth    seeded synthetic KITTI-shaped inputs
   dist     one-process-per-GPU pair sharding and RCCL metric gather
@@ -24,7 +26,8 @@ __all__ = ["ransac", "sweep", "regularize", "synth", "dist", "config", "validate
            "inverse_warp_autograd", "depth_head_autograd", "conv3_autograd", "batchnorm3_act_autograd",
            "context_refine_autograd", "dep_context_refine_autograd", "dep_context_unpack_grad",
            "conv2x_autograd", "conv2x_wgrad_f16", "conv2x_dgrad_f16",
-           "pack_dgrad_weights2x", "unpack_wgrad2x"]
+           "pack_dgrad_weights2x", "unpack_wgrad2x", "batchnorm2_act_autograd", "convbn2_autograd",
+           "basic_block_autograd"]
 
 
 def __getattr__(name):
@@ -42,7 +45,8 @@ def __getattr__(name):
         from . import context
         return getattr(context, name)
     if name in ("conv2x_autograd", "conv2x_wgrad_f16", "conv2x_dgrad_f16",
-                "pack_dgrad_weights2x", "unpack_wgrad2x"):
+                "pack_dgrad_weights2x", "unpack_wgrad2x", "batchnorm2_act_autograd", "convbn2_autograd",
+                "basic_block_autograd"):
         from . import feature
         return getattr(feature, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -139,6 +139,16 @@ _SIGS = [
     ("sfm_bn3_backward_f16_workspace_bytes", ctypes.c_size_t, [ctypes.c_int64]),
     ("sfm_bn3_backward_f16", ctypes.c_int,
      [_c_dp, _c_dp, ctypes.c_int64, _c_dp, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp, ctypes.c_size_t, _c_dp]),
+    ("sfm_bn2_stats_f16_workspace_bytes", ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    ("sfm_bn2_stats_f16", ctypes.c_int,
+     [_c_dp, ctypes.c_int64, ctypes.c_int, _c_dp, _c_dp, ctypes.c_double, _c_dp, _c_dp, ctypes.c_double, ctypes.c_int,
+      _c_dp, _c_dp, ctypes.c_size_t, _c_dp]),
+    ("sfm_bn2_apply_f16", ctypes.c_int,
+     [_c_dp, ctypes.c_int64, ctypes.c_int, _c_dp, _c_dp, ctypes.c_int, _c_dp, _c_dp]),
+    ("sfm_bn2_backward_f16_workspace_bytes", ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int]),
+    ("sfm_bn2_backward_f16", ctypes.c_int,
+     [_c_dp, _c_dp, ctypes.c_int64, ctypes.c_int, _c_dp, ctypes.c_int, ctypes.c_int, _c_dp, _c_dp, _c_dp,
+      ctypes.c_size_t, _c_dp]),
     ("sfm_to_channels_last_f16", ctypes.c_int,
      [_c_dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _c_dp, _c_dp]),
     ("sfm_conv3_f32", ctypes.c_int,

@@ -19,8 +19,12 @@ without libsfm_hip.so or a GPU the call raises.
 building block for training the CNN under float16 autocast (the reference
 trains in ``model.train()``, main.py:304): ``sfm_conv2x_f16`` forward,
 ``sfm_conv2x_wgrad_f16`` and ``sfm_conv2x_dgrad_f16`` backward
-(csrc/feature_bwd.hip).  The whole CNN on it, between torch's BatchNorm2d, is
-not built yet.
+(csrc/feature_bwd.hip).  ``batchnorm2_act_autograd`` is what stands between
+two of them: BatchNorm2d, ReLU and the residual add in float16 in both
+directions (csrc/bn2.hip: sfm_bn2_stats_f16, sfm_bn2_apply_f16,
+sfm_bn2_backward_f16); ``convbn2_autograd`` is one reference ``convbn`` and
+``basic_block_autograd`` one ``BasicBlock`` on the two.  The whole CNN on them
+(the pools' and the SPP upsample's backward) is not built yet.
 """
 import ctypes
 import weakref
@@ -507,3 +511,194 @@ def conv2x_autograd(x, weight, stride=1, dilation=1):
     _check_layer(int(weight.shape[2]), stride, dilation)
     return _Conv2x.apply(x, weight, int(stride), int(dilation))
 
+
+
+# --- BatchNorm2d, ReLU and the residual add in float16 (csrc/bn2.hip) ----------------
+BN2_CHANNELS = (32, 64, 128)
+
+
+def _bn2_operand(t, name, like=None):
+    _check_act(t, name)
+    if t.shape[3] not in BN2_CHANNELS:
+        raise RuntimeError(f"{name} must have 32, 64 or 128 channels")
+    if like is not None and t.shape != like.shape:
+        raise RuntimeError(f"{name} must have the shape of x")
+
+
+def bn2_stats_f16(x, gamma, beta, eps=1e-5, running_mean=None, running_var=None, momentum=0.1, training=True):
+    """sfm_bn2_stats_f16: x [n, h, w, C] float16 (channels last, C 32, 64 or
+    128), gamma / beta and the running statistics [C] float32 on x's device ->
+    stats [5, C] float32 (mean, biased variance, invstd, a, b).  In training
+    mode the running statistics, where given, are updated in place; in eval
+    mode they are read."""
+    _bn2_operand(x, "x")
+    lib = _lib.load()
+    C = x.shape[3]
+    pix = x.numel() // C
+    stats = torch.empty((5, C), dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(16, lib.sfm_bn2_stats_f16_workspace_bytes(pix, C, 1 if training else 0)), dtype=torch.uint8,
+                     device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.sfm_bn2_stats_f16(_lib.ptr(x), pix, C, _lib.ptr(gamma), _lib.ptr(beta), float(eps),
+                                   _lib.ptr(running_mean), _lib.ptr(running_var), float(momentum), 1 if training else 0,
+                                   _lib.ptr(stats), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device))
+        _lib.check(rc, "sfm_bn2_stats_f16")
+    if training:
+        for r in (running_mean, running_var):       # written through the raw pointer: tell autograd and the pack keys
+            if r is not None:
+                torch.autograd.graph.increment_version(r)
+    return stats
+
+
+def bn2_apply_f16(x, stats, residual=None, relu=False):
+    """sfm_bn2_apply_f16: f16(relu(fma(a, x, b)) + residual) with a, b from
+    ``stats`` [5, C] float32; x and residual [n, h, w, C] float16."""
+    _bn2_operand(x, "x")
+    if residual is not None:
+        _bn2_operand(residual, "residual", x)
+    C = x.shape[3]
+    out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().sfm_bn2_apply_f16(_lib.ptr(x), x.numel() // C, C, _lib.ptr(stats), _lib.ptr(residual),
+                                           1 if relu else 0, _lib.ptr(out), _lib.stream_ptr(x.device))
+        _lib.check(rc, "sfm_bn2_apply_f16")
+    return out
+
+
+def bn2_backward_f16(x, grad_out, stats, relu=False, training=True, need_grad_x=True):
+    """sfm_bn2_backward_f16 -> (grad_x float16 like x or None, grad_gamma_beta
+    [2, C] float32: dgamma, dbeta), from x and ``stats`` alone."""
+    _bn2_operand(x, "x")
+    _bn2_operand(grad_out, "grad_out", x)
+    lib = _lib.load()
+    C = x.shape[3]
+    pix = x.numel() // C
+    gx = torch.empty_like(x) if need_grad_x else None
+    ggb = torch.empty((2, C), dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(16, lib.sfm_bn2_backward_f16_workspace_bytes(pix, C)), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.sfm_bn2_backward_f16(_lib.ptr(x), _lib.ptr(grad_out), pix, C, _lib.ptr(stats), 1 if relu else 0,
+                                      1 if training else 0, _lib.ptr(gx), _lib.ptr(ggb), _lib.ptr(ws), ws.numel(),
+                                      _lib.stream_ptr(x.device))
+        _lib.check(rc, "sfm_bn2_backward_f16")
+    return gx, ggb
+
+
+class _BN2Act(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, bn, relu):
+        training = bool(bn.training)
+        stats = bn2_stats_f16(x, weight.detach(), bias.detach(), bn.eps, bn.running_mean, bn.running_var, bn.momentum,
+                              training)
+        if training:
+            bn.num_batches_tracked.add_(1)
+        out = bn2_apply_f16(x, stats, None if residual is None else residual.detach(), relu)
+        ctx.save_for_backward(x, stats)
+        ctx.relu, ctx.training, ctx.param_dtypes = relu, training, (weight.dtype, bias.dtype)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, stats = ctx.saved_tensors
+        need_x, need_w, need_b, need_r = ctx.needs_input_grad[:4]
+        gx = gw = gb = None
+        if need_x or need_w or need_b:
+            gx, ggb = bn2_backward_f16(x, g.to(torch.float16).contiguous(), stats, ctx.relu, ctx.training, need_x)
+            gw = ggb[0].to(ctx.param_dtypes[0]) if need_w else None
+            gb = ggb[1].to(ctx.param_dtypes[1]) if need_b else None
+        return gx, gw, gb, (g if need_r else None), None, None
+
+
+def batchnorm2_act_autograd(x, bn, relu=False, residual=None):
+    """``bn`` (an nn.BatchNorm2d of 32, 64 or 128 features), then ReLU if
+    ``relu``, then ``+ residual``, on libsfm_hip in both directions: x and
+    residual [n, h, w, C] float16 on the device, channels last -> the same
+    shape, float16, rounded once (sfm_bn2_stats_f16, sfm_bn2_apply_f16).  The
+    contract of ``regularize.batchnorm3_act_autograd``: the module's mode, eps,
+    momentum and affine parameters are honoured; training mode takes batch
+    statistics, updates the running statistics in place by torch's rule and
+    increments num_batches_tracked; eval mode reads the running statistics.
+    Only x and the 5 x C floats of statistics are saved; the backward
+    (sfm_bn2_backward_f16) returns gradients for x, bn.weight, bn.bias and the
+    residual (the output gradient itself), each only where needed.  A module
+    that is not the stock affine one with running statistics and a fixed
+    momentum, or that carries forward hooks, raises; so does a CPU tensor."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float16 and x.dim() == 4 and
+            x.shape[3] in BN2_CHANNELS):
+        raise RuntimeError("batchnorm2_act_autograd needs a [n, h, w, C] float16 device tensor, C 32, 64 or 128 (HIP "
+                           "path, no CPU fallback)")
+    C = x.shape[3]
+    if type(bn) is not nn.BatchNorm2d or bn.num_features != C:
+        raise RuntimeError(f"bn must be an nn.BatchNorm2d of x's {C} channels")
+    if not bn.affine or not bn.track_running_stats or bn.momentum is None or bn.running_mean is None:
+        raise RuntimeError("bn must be the stock module: affine=True, track_running_stats=True and a fixed momentum")
+    if bn._forward_hooks or bn._forward_pre_hooks:
+        raise RuntimeError("bn carries forward hooks, which the HIP route would not call")
+    for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var):
+        if not (t.device == x.device and t.dtype == torch.float32 and t.is_contiguous()):
+            raise RuntimeError("bn's parameters and running statistics must be float32 on x's device")
+    if x.numel() // C < 2 and bn.training:
+        raise RuntimeError("training-mode batch statistics need more than one value per channel")
+    if residual is not None and not (isinstance(residual, torch.Tensor) and residual.is_cuda and
+                                     residual.dtype == torch.float16 and residual.shape == x.shape):
+        raise RuntimeError("residual must be a float16 device tensor of x's shape")
+    return _BN2Act.apply(x.contiguous(), bn.weight, bn.bias, None if residual is None else residual.contiguous(), bn,
+                         bool(relu))
+
+
+def _convbn_layer(seq, what):
+    """(conv, bn) of a reference convbn, checked by ``_conv_bn`` against its own
+    Conv2d's geometry and by ``_check_layer`` against the layer set."""
+    mods = list(seq) if isinstance(seq, nn.Sequential) else []
+    if len(mods) != 2 or not isinstance(mods[0], nn.Conv2d):
+        raise FeatureLayoutError(f"{what}: expected Conv2d + BatchNorm2d")
+    c = mods[0]
+    k, stride, dilation = int(c.kernel_size[0]), int(c.stride[0]), int(c.dilation[0])
+    _check_layer(k, stride, dilation)
+    conv, bn = _conv_bn(seq, c.in_channels, c.out_channels, k, stride, dilation, what)
+    if conv.out_channels not in BN2_CHANNELS or conv.in_channels % 32:
+        raise FeatureLayoutError(f"{what}: {conv.in_channels} -> {conv.out_channels} channels; the output must have 32, "
+                                 f"64 or 128 and the input a multiple of 32")
+    return conv, bn
+
+
+def convbn2_autograd(x, seq, relu=False, residual=None):
+    """One reference ``convbn`` (models/submodule.py:11-14: Sequential(Conv2d,
+    BatchNorm2d), no conv bias) with a backward, all on libsfm_hip:
+    ``conv2x_autograd`` on the Conv2d's weight, then ``batchnorm2_act_autograd``
+    on the BatchNorm2d with the ReLU and the residual.  x [n, h, w, cin]
+    float16 channels last on the device -> [n, hout, wout, cout] float16."""
+    conv, bn = _convbn_layer(seq, "convbn")
+    y = conv2x_autograd(x, conv.weight, int(conv.stride[0]), int(conv.dilation[0]))
+    return batchnorm2_act_autograd(y, bn, relu, residual)
+
+
+def basic_block_autograd(block, x):
+    """One reference BasicBlock (models/submodule.py:22-44;
+    ``sfm_amd.psnet._Residual``) with a backward, on ``convbn2_autograd``:
+    conv1 + ReLU, conv2, the 1 x 1 ``downsample`` convbn of x where the block
+    has one, and ``+ x`` with no ReLU after it (submodule.py:35-44).  x [n, h,
+    w, cin] float16 channels last on the device -> [n, hout, wout, cout]
+    float16.  No torch batch_norm or convolution runs on the device."""
+    c1 = getattr(block, "conv1", None)
+    if not isinstance(c1, nn.Sequential) or len(c1) != 2 or not isinstance(c1[1], nn.ReLU) or \
+            not hasattr(block, "conv2") or not hasattr(block, "downsample"):
+        raise FeatureLayoutError("block: expected conv1 = convbn + ReLU, conv2 = convbn and a downsample attribute")
+    conv1, _ = _convbn_layer(c1[0], "block.conv1")
+    conv2, _ = _convbn_layer(block.conv2, "block.conv2")
+    if tuple(conv2.stride) != (1, 1) or conv2.in_channels != conv1.out_channels or \
+            conv2.out_channels != conv1.out_channels:
+        raise FeatureLayoutError("block.conv2: expected stride 1 and conv1's output channels on both sides")
+    if block.downsample is None:
+        if tuple(conv1.stride) != (1, 1) or conv1.in_channels != conv1.out_channels:
+            raise FeatureLayoutError("block: a strided or widening block needs its downsample")
+        shortcut = x
+    else:
+        ds, _ = _convbn_layer(block.downsample, "block.downsample")
+        if tuple(ds.kernel_size) != (1, 1) or ds.stride != conv1.stride or ds.in_channels != conv1.in_channels or \
+                ds.out_channels != conv1.out_channels:
+            raise FeatureLayoutError("block.downsample: expected a 1 x 1 convbn of conv1's stride and channels")
+        shortcut = convbn2_autograd(x, block.downsample)
+    y = convbn2_autograd(x, c1[0], relu=True)
+    return convbn2_autograd(y, block.conv2, residual=shortcut)

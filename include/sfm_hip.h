@@ -693,6 +693,46 @@ size_t sfm_bn3_backward_f16_workspace_bytes(int64_t voxels);
 int sfm_bn3_backward_f16(const void* x, const void* grad_out, int64_t voxels, const float* stats, int relu, int training,
                          void* grad_x, float* grad_gamma_beta, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same three entries for the feature CNN (and context_net under
+ * IND_CONTEXT): the BatchNorm2d of convbn (models/submodule.py:11-14), the ReLU
+ * and the "+ x" of BasicBlock (models/submodule.py:22-44), in float16, forward
+ * and backward -- what stands between two sfm_conv2x_f16 layers of a training
+ * step.  x is what sfm_conv2x_f16 writes: pixels x channels float16 channels
+ * last (pixels = images x h x w, an int64_t: every offset is 64-bit), channels
+ * 32, 64 or 128 (anything else is refused: "channels must be 32, 64 or 128").
+ * The kernels are the ones sfm_bn3_* runs, instantiated per channel count
+ * (csrc/bn_act.h): the same arithmetic, order of additions, alignment and
+ * aliasing rules, refusals and reproducibility; gamma, beta and the running
+ * statistics hold `channels` float32, stats 5 x channels.
+ *
+ * sfm_bn2_stats_f16: as sfm_bn3_stats_f16; training 1 needs pixels >= 2.  The
+ * number of reducing blocks is min(ceil(pixels / (4096 / channels)), 512), or
+ * the tuning key bn_blocks; a partial is 2 x channels doubles, so the workspace
+ * is blocks x 2 x channels x 8 bytes.  Profile name "bn2_stats". */
+size_t sfm_bn2_stats_f16_workspace_bytes(int64_t pixels, int channels, int training);
+int sfm_bn2_stats_f16(const void* x, int64_t pixels, int channels, const float* gamma, const float* beta, double eps,
+                      float* running_mean, float* running_var, double momentum, int training, float* stats,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* One BatchNorm2d with its activation and residual (models/submodule.py:11-14;
+ * the BasicBlock of models/submodule.py:22-44) in one pass: out =
+ * f16(relu(fma(a, x, b)) + residual), the ReLU first and then the add, a and b
+ * rows 3 and 4 of `stats` [dev] 5 x channels, residual [dev] like x or NULL.
+ * float32, rounded once.  Profile name "bn2_apply". */
+int sfm_bn2_apply_f16(const void* x, int64_t pixels, int channels, const float* stats, const void* residual, int relu,
+                      void* out, void* stream);
+
+/* The backward of sfm_bn2_apply_f16 on sfm_bn2_stats_f16's statistics (the
+ * gradient of models/submodule.py:11-14 inside models/submodule.py:22-44), from
+ * x and `stats` alone, as sfm_bn3_backward_f16: grad_gamma_beta [dev]
+ * 2 x channels float32 (dgamma, then dbeta), grad_x [dev] like x or NULL, the
+ * workspace sfm_bn2_backward_f16_workspace_bytes(pixels, channels) bytes.  Two
+ * launches, no atomics.  Profile name "bn2_bwd". */
+size_t sfm_bn2_backward_f16_workspace_bytes(int64_t pixels, int channels);
+int sfm_bn2_backward_f16(const void* x, const void* grad_out, int64_t pixels, int channels, const float* stats, int relu,
+                         int training, void* grad_x, float* grad_gamma_beta, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* The same layer at the reference's precision (conv_precision "fp32"):
  * float32 operands on v_mfma_f32_32x32x2_f32 (an exact fmaf chain: products
  * and sums round as float32 arithmetic; only the summation order differs from
